@@ -24,13 +24,25 @@ ranks).
 
 Extra objects on the JSON line: ``roofline`` (dominant kernel of the timed
 region, HIP-event timed; ``traffic`` is measured only with ``--pmc-traffic``,
-which re-runs this command under ``rocprofv3 --pmc`` in child processes),
-``roofline_contains`` (the north star's streaming Ellipsoid.contains kernel),
+which re-runs this command under ``rocprofv3 --pmc`` in child processes).
+A plain run stops there: set-up, warm-up, the K timed steps, the outputs
+(``--dump-outputs``) and the result line.  ``--full`` adds the measurements
+that take runs of their own, after the timed steps:
+``roofline_contains`` (the north star's streaming Ellipsoid.contains kernel,
+and ``roofline_contains_d100`` at n_dim 100),
 ``roofline_draw`` (the proposal draw: proposals/s, bytes written against HBM,
-fp64 vector operations against the peak),
+fp64 vector operations against the peak), ``roofline_two_stage_d100``,
+``mfma_f64_probe_tflops``,
 ``cpu_baseline`` (the CPU oracle continuing the same sampler state through
 the reference's multiprocess-pool path on all host cores, and on one core,
 for a bounded time).
+
+``--dump-outputs DIR`` writes what the last timed step computed as
+``DIR/<name>.npy`` (float64): ``points`` and ``log_l``, the rows the step added
+to its shell (a fixed, seeded sample of them if they exceed 64 MB),
+``shell_index``, the shell statistics of the sampler after the step
+(``shell_n``, ``shell_n_eff``, ``shell_log_l``, ``shell_log_v``) and ``log_z``,
+``n_eff``.  The inputs depend only on the arguments (``--seed``).
 """
 
 import argparse
@@ -98,7 +110,51 @@ def parse():
     p.add_argument('--force-comm', action='store_true',
                    help='functional test: run the collective code path even '
                         'with a single rank')
-    return p.parse_args()
+    p.add_argument('--full', action='store_true',
+                   help='after the timed steps, also run the kernel '
+                        'micro-benchmarks (roofline_contains, '
+                        'roofline_contains_d100, roofline_draw, '
+                        'roofline_two_stage_d100, mfma_f64_probe_tflops) and '
+                        'the CPU baseline')
+    p.add_argument('--dump-outputs', metavar='DIR',
+                   help='write what the last timed step computed as '
+                        'DIR/<name>.npy (float64, at most 64 MB in all)')
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error('--steps must be at least 1')
+    return args
+
+
+DUMP_BYTES_MAX = 64 * 10**6     # all files of --dump-outputs, headers included
+
+
+def dump_outputs(out_dir, sampler, shell, pts_start, ll_start):
+    """The arrays a caller of the timed path holds after its last step: the
+    points and log L that ``add_samples(shell)`` appended to the shell (rows
+    ``pts_start`` / ``ll_start`` on) and the sampler's shell statistics."""
+    pts = sampler._pts[shell].view()[pts_start:].cpu().numpy()
+    log_l = np.asarray(sampler.log_l[shell][ll_start:], dtype=np.float64)
+    assert pts.shape[0] == log_l.shape[0], (pts.shape, log_l.shape)
+    arrays = dict(
+        shell_index=np.array([shell], dtype=np.float64),
+        shell_n=np.asarray(sampler.shell_n, dtype=np.float64),
+        shell_n_eff=np.asarray(sampler.shell_n_eff, dtype=np.float64),
+        shell_log_l=np.asarray(sampler.shell_log_l, dtype=np.float64),
+        shell_log_v=np.asarray(sampler.shell_log_v, dtype=np.float64),
+        log_z=np.array([sampler.log_z], dtype=np.float64),
+        n_eff=np.array([sampler.n_eff], dtype=np.float64))
+    # (4 KB per file for the .npy headers)
+    room = DUMP_BYTES_MAX - sum(a.nbytes + 4096 for a in arrays.values()) \
+        - 2 * 4096
+    row_bytes = pts.itemsize * (pts.shape[1] + 1)
+    if pts.shape[0] * row_bytes > room:
+        keep = np.sort(np.random.default_rng(0).choice(
+            pts.shape[0], room // row_bytes, replace=False))
+        pts, log_l = pts[keep], log_l[keep]
+    arrays.update(points=pts, log_l=log_l)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 class NumpyGaussian:
@@ -302,6 +358,13 @@ def pmc_traffic(argv):
     import tempfile
     if shutil.which('rocprofv3') is None:
         return None
+    # the children write no outputs (the parent does)
+    argv = list(argv)
+    for i, a in reversed(list(enumerate(argv))):
+        if a == '--dump-outputs':
+            del argv[i:i + 2]
+        elif a.startswith('--dump-outputs='):
+            del argv[i]
     totals = {}
     calls = None
     for counter in ('FETCH_SIZE', 'WRITE_SIZE'):
@@ -511,11 +574,16 @@ def main():
     if comm is not None:
         sampler.n_batch = args.n_batch_setup * world
 
+    # shell of the latest step and where its rows start (--dump-outputs)
+    last_step = {}
+
     def step():
         if np.any(sampler.shell_n < 1):
             shell = int(np.flatnonzero(sampler.shell_n < 1)[0])
         else:
             shell = sampler._next_shell()
+        last_step.update(shell=shell, pts_start=sampler._pts[shell].n,
+                         ll_start=len(sampler.log_l[shell]))
         sampler.add_samples(shell)
 
     def proposals():
@@ -561,6 +629,8 @@ def main():
         comm.barrier()
         dt = comm.max_float(dt, 'cuda')
     n_eff1, n_like1, prop1 = sampler.n_eff, sampler.n_like, proposals()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sampler, **last_step)
     kernels = ktimer.totals()
     work = counters.read()
     dispatches = {k: device.DISPATCHES[k] - disp0[k] for k in disp0}
@@ -683,7 +753,7 @@ def main():
         per_rank_seconds=rank_phases,
         roofline=roofline)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # the north star's named kernel: streaming Ellipsoid.contains
         nb = sampler.bounds[-1].neural_bounds[0].outer_bound
         ell = Ellipsoid.from_params(nb.c, nb.B, nb.B_inv, nb.A)
@@ -796,6 +866,7 @@ def main():
             out['cpu_baseline'] = cpu_baseline(
                 sampler, NumpyGaussian(np.full(d, 0.5), 0.05),
                 args.cpu_seconds, args.cpu_cores)
+    if rank == 0:
         print(json.dumps(out))
     if comm is not None:
         comm.barrier()

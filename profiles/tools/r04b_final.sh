@@ -7,7 +7,7 @@ O=$R/gpurun_out/r04b_final
 mkdir -p $O
 cd $R
 # 1. the bench line
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 tail -c 300 $O/bench.json; echo
 # 2. kernel statistics of the timed region
 cd /tmp && rm -rf /tmp/r04b_bench

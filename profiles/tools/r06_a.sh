@@ -4,8 +4,8 @@ O=gpurun_out/r06a; mkdir -p $O
 python -m pytest tests/test_hip_parity.py -x -q -k "two_stage or gmm or list_eval or accept_routes or pipelined or union_proposals" > $O/tests_parity.txt 2>&1; tail -3 $O/tests_parity.txt
 python -m pytest tests/test_sampler_gpu.py tests/test_sampler_behaviour_gpu.py tests/test_fuzz_gpu.py -x -q > $O/tests_sampler.txt 2>&1; tail -3 $O/tests_sampler.txt
 for i in 1 2; do
-  NB_PREFETCH=0 python bench.py --no-cpu-baseline > $O/bench_noprefetch_$i.json 2>/dev/null
-  NB_PREFETCH=1 python bench.py --no-cpu-baseline > $O/bench_prefetch_$i.json 2>/dev/null
+  NB_PREFETCH=0 python bench.py --full --no-cpu-baseline > $O/bench_noprefetch_$i.json 2>/dev/null
+  NB_PREFETCH=1 python bench.py --full --no-cpu-baseline > $O/bench_prefetch_$i.json 2>/dev/null
 done
 python - <<'PY'
 import json, glob

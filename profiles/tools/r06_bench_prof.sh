@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round-6 evidence for the bench line: (1) the plain default run, (2) the same
+# Round-6 evidence for the bench line: (1) the default run with --full, (2) the
 # command under rocprofv3 --kernel-trace --stats restricted to the timed
 # region, (3) HBM traffic of the bound-evaluation kernels (bench.py
 # --pmc-traffic: FETCH_SIZE / WRITE_SIZE in separate child passes), (4)
@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$R/gpurun_out/r06
 mkdir -p $OUT
 cd $R
-python bench.py > $OUT/bench_r06.json 2> $OUT/bench_r06.err
+python bench.py --full > $OUT/bench_r06.json 2> $OUT/bench_r06.err
 tail -c 400 $OUT/bench_r06.json
 cd /tmp
 rm -rf /tmp/r06_bench

@@ -331,6 +331,39 @@ def test_bench_over_rccl_single_rank():
     assert res['per_rank_seconds']['timed_steps'][0]['collectives'] > 0
 
 
+def test_bench_dumps_the_last_step(tmp_path):
+    """bench.py --dump-outputs: the rows the last timed step added, with
+    their log L (the benchmark's Gaussian at those points), the shell
+    statistics and the evidence of the result line, as float64 .npy files;
+    a plain run carries none of the --full measurements."""
+    import subprocess
+    import sys
+    from conftest import ROOT
+    from bench import NumpyGaussian
+    out_dir = tmp_path / 'outputs'
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1',
+           '--steps', '3', '--warmup', '1', '--dim', '6', '--n-live', '300',
+           '--n-batch', '2048', '--n-batch-setup', '512', '--dump-outputs',
+           str(out_dir)]
+    out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True,
+                         timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = [ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1]
+    res = json.loads(line)
+    assert res['steps'] == 3 and res['ms_per_step'] > 0
+    assert not any(k.startswith(('roofline_', 'cpu_', 'mfma_')) for k in res)
+    got = {p.stem: np.load(p) for p in out_dir.glob('*.npy')}
+    assert all(a.dtype == np.float64 for a in got.values())
+    pts, log_l = got['points'], got['log_l']
+    assert log_l.shape[0] > 0 and pts.shape == (log_l.shape[0], 6)
+    assert np.all((pts >= 0) & (pts <= 1))
+    want = NumpyGaussian(np.full(6, 0.5), 0.05)(pts)
+    assert np.allclose(log_l, want, rtol=1e-12, atol=1e-9)
+    assert got['log_z'][0] == res['log_z'] and got['n_eff'][0] == res['n_eff']
+    assert got['shell_n'].shape == (res['n_bounds'],)
+    assert 0 <= got['shell_index'][0] < res['n_bounds']
+
+
 def _run_sharded(world, *extra):
     import subprocess
     import sys
