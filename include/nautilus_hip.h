@@ -229,7 +229,12 @@ int nb_trainer_create_fleet(int32_t n_dim, int32_t n_networks,
                             nb_trainer** out);
 /* Optional: MLPRegressor hyper-parameters (defaults are the reference's,
  * neural.py:79-81: lr 1e-2, betas 0.9/0.999, eps 1e-8, batch 200, max_iter
- * 10000, n_iter_no_change 10, tol 0).                                       */
+ * 10000, n_iter_no_change 10, tol 0).  batch: 1 .. NB_TRAIN_MAX_BATCH rows,
+ * clipped to a network's rows on the device (scikit-learn's rule); up to 200
+ * rows the stash of the trainer keeps its layout of nb_trainer_create, above
+ * that it is laid out again for the batch (the call then waits for the
+ * device).  Call it before nb_trainer_run*, not while a run is in flight.   */
+#define NB_TRAIN_MAX_BATCH 4096
 int nb_trainer_set_hparams(nb_trainer* t, double lr, double beta1,
                            double beta2, double epsilon, int32_t batch,
                            int32_t max_iter, int32_t n_iter_no_change,

@@ -25,6 +25,15 @@
 //
 // Minibatch order comes from the host (numpy RandomState shuffles identical to
 // sklearn's), so the device sees exactly the reference's data order.
+//
+// Minibatches of up to 200 rows (the reference's default) run on a stash of
+// G_ROWT row tiles laid out at compile time.  Larger ones, up to
+// NB_TRAIN_MAX_BATCH, run the LARGE instantiations of the same kernels: the
+// row-tile count is a property of the trainer (TrainArgs::rowt, the stash is
+// re-laid out for it by nb_trainer_set_hparams), an FB workgroup of the
+// resident kernel loops over the row tiles slot, slot + 32, ..., and a G job
+// contracts the row tiles of the minibatch in chunks of G_PAIRS per wavefront
+// (same fixed order of summation, no atomics).
 #include "nb_common.h"
 #include "../../include/nautilus_hip.h"
 
@@ -44,6 +53,8 @@ typedef double nb_d2 __attribute__((ext_vector_type(2)));
 constexpr int MAXB = 208;        // minibatch rows padded to 16 (batch <= 200)
 constexpr int LD1 = 112, LD2 = 64, LD3 = 32, LD4 = 16;
 constexpr int G_ROWT = MAXB / 16;   // 16-row tiles of a minibatch
+constexpr int SMALL_BATCH = 200;    // largest batch of the compile-time layout
+static_assert(NB_TRAIN_MAX_BATCH % 16 == 0, "row tiles of the largest batch");
 // transposed copies of the weight tiles of layers 2-4 (operands of the
 // backward products): [ht][kt] tiles, element (hh, kk) = W[16 kt + kk][16 ht + hh]
 constexpr int WT2 = 0;
@@ -137,6 +148,7 @@ struct TrainArgs {
   long long n;
   int n_dim, kt1, n_epochs, max_iter, n_iter_no_change, batch;
   double tol, lr, b1, b2, eps;
+  int rowt;             // LARGE: 16-row tiles of the stash (G_ROWT otherwise)
 };
 
 __device__ __forceinline__ NetData shared_data(const TrainArgs& a, int net) {
@@ -509,23 +521,41 @@ struct FbLds {
 struct StashPtrs {
   nb_gd *A0, *A1, *A2, *A3, *D1, *D2, *D3, *D4;
 };
-__device__ __forceinline__ StashPtrs stash_ptrs(const NetState& st, int ld0) {
+// doubles of a stash of `rows` rows (a multiple of 16) ...
+__host__ __device__ constexpr long long stash_doubles(long long rows, int ld0) {
+  return rows * (ld0 + 2 * (LD1 + LD2 + LD3) + LD4);
+}
+// ... of `rows` = MAXB, or 16 * TrainArgs::rowt for the LARGE kernels, which
+// keep the loss partials of the row tiles behind it (the small layout has
+// them in scal[8 ..])
+template <bool LARGE>
+__device__ __forceinline__ int stash_rows(const TrainArgs& a) {
+  return LARGE ? 16 * a.rowt : MAXB;
+}
+__device__ __forceinline__ StashPtrs stash_ptrs(const NetState& st, int ld0,
+                                                int rows) {
   StashPtrs p;
   p.A0 = st.stash;
-  p.A1 = p.A0 + MAXB * ld0;
-  p.A2 = p.A1 + MAXB * LD1;
-  p.A3 = p.A2 + MAXB * LD2;
-  p.D1 = p.A3 + MAXB * LD3;
-  p.D2 = p.D1 + MAXB * LD1;
-  p.D3 = p.D2 + MAXB * LD2;
-  p.D4 = p.D3 + MAXB * LD3;
+  p.A1 = p.A0 + rows * ld0;
+  p.A2 = p.A1 + rows * LD1;
+  p.A3 = p.A2 + rows * LD2;
+  p.D1 = p.A3 + rows * LD3;
+  p.D2 = p.D1 + rows * LD1;
+  p.D3 = p.D2 + rows * LD2;
+  p.D4 = p.D3 + rows * LD3;
   return p;
+}
+template <bool LARGE>
+__device__ __forceinline__ nb_gd* loss_parts(const TrainArgs& a,
+                                             const NetState& st) {
+  return LARGE ? st.stash + stash_doubles(16 * a.rowt, 16 * a.kt1)
+               : st.scal + 8;
 }
 
 // `upper_ready` is called by wavefront 3 once the activations of the layers
 // 1-3 and the deltas of the layers 2-4 of this tile are in the L2 (all of the
 // stash except the layer-1 deltas).
-template <int KT1, bool CHECK_DONE, class Hook>
+template <int KT1, bool CHECK_DONE, bool LARGE, class Hook>
 __device__ __forceinline__ void fb_body(const TrainArgs& a, const NetState& st,
                                         int net, int tile, int nb,
                                         const FbRows<KT1>& rows, double* lds,
@@ -564,7 +594,7 @@ __device__ __forceinline__ void fb_body(const TrainArgs& a, const NetState& st,
   constexpr unsigned W3 = W2 + NB_HT1 * NB_HT2 * NB_TILE;
   constexpr unsigned W4 = W3 + NB_HT2 * NB_HT3 * NB_TILE;
   constexpr unsigned T2 = WT2, T3 = WT3, T4 = WT4;
-  const StashPtrs sp = stash_ptrs(st, LD0);
+  const StashPtrs sp = stash_ptrs(st, LD0, stash_rows<LARGE>(a));
 
   const int pt = tile * 16 + li;
   const bool valid = pt < nb;
@@ -845,7 +875,7 @@ __device__ __forceinline__ void fb_body(const TrainArgs& a, const NetState& st,
   // memory queue and every stage waited for a store acknowledgement; the
   // wavefronts that flush now have issued their last operand load before.)
   flush_stash(sD1, sp.D1, LD1, LD1, tile, tid);
-  if (wave == 0 && lane == 0) st.scal[8 + tile] = lp;
+  if (wave == 0 && lane == 0) loss_parts<LARGE>(a, st)[tile] = lp;
   FB_STAMP(19);
 }
 
@@ -855,7 +885,7 @@ __device__ __forceinline__ void fb_body(const TrainArgs& a, const NetState& st,
 // times zero deltas).
 __device__ __forceinline__ void fb_clear_deltas(const NetState& st, int ld0,
                                                 int tile) {
-  const StashPtrs sp = stash_ptrs(st, ld0);
+  const StashPtrs sp = stash_ptrs(st, ld0, MAXB);
   const unsigned tid = threadIdx.x;
   nb_gd* d1 = sp.D1 + tile * 16 * LD1;
   nb_gd* d2 = sp.D2 + tile * 16 * LD2;
@@ -867,14 +897,15 @@ __device__ __forceinline__ void fb_clear_deltas(const NetState& st, int ld0,
   if (tid < 16 * LD4) d4[tid] = 0.0;
 }
 
-template <int KT1>
+template <int KT1, bool LARGE>
 __global__ void __launch_bounds__(256)
 nb_train_fb_kernel(TrainArgs a, int ep, long long start, int nb) {
   __shared__ __attribute__((aligned(16))) double lds[FbLds<KT1>::TOTAL];
   const NetState st = a.nets[blockIdx.y];
   const int tile = (int)blockIdx.x;
   if (tile * 16 >= nb) {
-    if (st.scal[4] == 0.0) fb_clear_deltas(st, 16 * KT1, tile);
+    // (LARGE: G contracts the row tiles of the minibatch only)
+    if (!LARGE && st.scal[4] == 0.0) fb_clear_deltas(st, 16 * KT1, tile);
     return;
   }
   for (int i = threadIdx.x; i < FbLds<KT1>::LD0 * LS; i += 256) lds[i] = 0.0;
@@ -883,19 +914,33 @@ nb_train_fb_kernel(TrainArgs a, int ep, long long start, int nb) {
   const NetData nd = shared_data(a, (int)blockIdx.y);
   fb_gather<KT1>(nd, a.n_dim, tile, nb, fb_row_index(nd, tile, ep, start, nb),
                  rows);
-  fb_body<KT1, true>(a, st, (int)blockIdx.y, tile, nb, rows, lds, []() {});
+  fb_body<KT1, true, LARGE>(a, st, (int)blockIdx.y, tile, nb, rows, lds,
+                           []() {});
 }
 
 // ---- G: dW of 16x16 weight tiles over the minibatch + Adam ------------------
 // the step's loss partials folded into the epoch sum, in tile order
-// (deterministic); one wavefront, partial i in lane i
-__device__ __forceinline__ void loss_fold(const NetState& st, int nb,
+// (deterministic); one wavefront, partial i in lane i (LARGE: in rounds of 64)
+template <bool LARGE>
+__device__ __forceinline__ void loss_fold(const TrainArgs& a,
+                                          const NetState& st, int nb,
                                           int lane) {
   const int n_tiles = (nb + 15) >> 4;
-  const double p = (lane < n_tiles) ? ld_xcd(&st.scal[8 + lane]) : 0.0;
-  double acc = ld_xcd(&st.scal[5]);
-  for (int i = 0; i < n_tiles; ++i) acc += __shfl(p, i);
-  if (lane == 0) st.scal[5] = acc;
+  const nb_gd* part = loss_parts<LARGE>(a, st);
+  if constexpr (!LARGE) {
+    const double p = (lane < n_tiles) ? ld_xcd(&part[lane]) : 0.0;
+    double acc = ld_xcd(&st.scal[5]);
+    for (int i = 0; i < n_tiles; ++i) acc += __shfl(p, i);
+    if (lane == 0) st.scal[5] = acc;
+  } else {
+    double acc = ld_xcd(&st.scal[5]);
+    for (int i0 = 0; i0 < n_tiles; i0 += 64) {
+      const double p = (i0 + lane < n_tiles) ? ld_xcd(&part[i0 + lane]) : 0.0;
+      const int m = n_tiles - i0 < 64 ? n_tiles - i0 : 64;
+      for (int i = 0; i < m; ++i) acc += __shfl(p, i);
+    }
+    if (lane == 0) st.scal[5] = acc;
+  }
 }
 
 // (hi + lo) *= b for an unevaluated sum hi + lo: the product hi * b exactly
@@ -937,8 +982,8 @@ struct GLayer {
 
 // (wave-uniform: scalar registers)
 __device__ __forceinline__ GLayer g_layer(const NetState& st, int kt1,
-                                          int layer) {
-  const StashPtrs sp = stash_ptrs(st, 16 * kt1);
+                                          int layer, int rows) {
+  const StashPtrs sp = stash_ptrs(st, 16 * kt1, rows);
   const int n_gt1 = kt1 * NB_HT1, n_gt2 = NB_HT1 * NB_HT2,
             n_gt3 = NB_HT2 * NB_HT3;
   GLayer g;
@@ -995,6 +1040,26 @@ __device__ __forceinline__ void g_load_col(const nb_gd* base, int ld, int col,
   }
 }
 
+// LARGE: the pairs it0 .. it0 + G_PAIRS - 1 of the wavefront (row tiles
+// wave / 2 + 2 it, as above); pairs past the n_rt row tiles of the minibatch
+// load row tile 0 again and scale it to zero (unconditional loads)
+__device__ __forceinline__ void g_load_chunk(const nb_gd* base, int ld,
+                                             int col, int wave, unsigned lane,
+                                             int it0, int n_rt, nb_d2* v) {
+  const __amdgpu_buffer_rsrc_t rsrc = tile_rsrc(uniform_ptr(base));
+  const unsigned voff = lane * 16;
+  const unsigned cofs = (unsigned)(col * 2 + (wave & 1)) * 128;
+#pragma unroll
+  for (int it = 0; it < G_PAIRS; ++it) {
+    const int rt = (wave >> 1) + 2 * (it0 + it);
+    const bool in = rt < n_rt;
+    const unsigned soff = ((unsigned)(in ? rt : 0) * 16 * ld + cofs) * 8;
+    const double keep = in ? 1.0 : 0.0;
+    const nb_d2 w = ld_xcd2(rsrc, voff, soff);
+    v[it] = nb_d2{w.x * keep, w.y * keep};
+  }
+}
+
 #ifdef NB_TRAIN_TIMING
 #define G_TIMED (net == 0 && slot == NB_TRAIN_TIMING_SLOT)
 #define G_STAMP(i) NB_STAMP(timed, i)
@@ -1030,7 +1095,7 @@ __device__ __forceinline__ GJob g_job_record(const nb_gi* jobs, int job) {
 // so that the wait in front of every MFMA chain is exactly for its operands --
 // with the shape as run-time conditions around the loads the first chain
 // waited for the whole memory queue)
-template <int NK, int NH, class Hook>
+template <int NK, int NH, bool LARGE, class Hook>
 __device__ __forceinline__ void g_job_shape(const TrainArgs& a,
                                             const NetState& st,
                                             const GJob& jb, int nb,
@@ -1046,7 +1111,7 @@ __device__ __forceinline__ void g_job_shape(const TrainArgs& a,
   const unsigned li = lane & 15, lg = lane >> 4;
   const int layer = jb.layer, kt0 = jb.kt0, ht0 = jb.ht0;
   constexpr int nk = NK, nh = NH;
-  const GLayer g = g_layer(st, a.kt1, layer);
+  const GLayer g = g_layer(st, a.kt1, layer, stash_rows<LARGE>(a));
   G_STAMP(33);
   // (first in the memory queue: vector memory returns in order, and every
   // load behind the operands is conditional -- the wait in front of the first
@@ -1060,11 +1125,13 @@ __device__ __forceinline__ void g_job_shape(const TrainArgs& a,
   // 2: (kt0 + 1, ht0); 3: (kt0 + 1, ht0 + 1), or (kt0 + 2, ht0) for nk = 3.
   constexpr bool three = nk == 3;
   nb_d2 c0[G_PAIRS], c1[G_PAIRS], c2[G_PAIRS], cx[G_PAIRS];
-  g_load_col(g.as, g.lda, kt0, wave, lane, c0);
-  g_load_col(g.bs, g.ldb, ht0, wave, lane, c1);
-  if (nk > 1) g_load_col(g.as, g.lda, kt0 + 1, wave, lane, c2);
-  if (three) g_load_col(g.as, g.lda, kt0 + 2, wave, lane, cx);
-  else if (nh > 1) g_load_col(g.bs, g.ldb, ht0 + 1, wave, lane, cx);
+  if constexpr (!LARGE) {
+    g_load_col(g.as, g.lda, kt0, wave, lane, c0);
+    g_load_col(g.bs, g.ldb, ht0, wave, lane, c1);
+    if (nk > 1) g_load_col(g.as, g.lda, kt0 + 1, wave, lane, c2);
+    if (three) g_load_col(g.as, g.lda, kt0 + 2, wave, lane, cx);
+    else if (nh > 1) g_load_col(g.bs, g.ldb, ht0 + 1, wave, lane, cx);
+  }
   G_STAMP(30);
   // this lane's element of every tile of the job: row lg + 4 wave, column li
   const unsigned eoff = (lg + 4 * wave) * 16 + li;     // moments: row major
@@ -1084,24 +1151,64 @@ __device__ __forceinline__ void g_job_shape(const TrainArgs& a,
       m_old[t] = ld_xcd(&(st.M + woff)[eoff]);
       v_old[t] = ld_xcd(&(st.V + woff)[eoff]);
     }
-  auto chain = [&](const nb_d2* av, const nb_d2* bv, int t)
-                   __attribute__((always_inline)) {
-    nb_d4 acc = {0.0, 0.0, 0.0, 0.0};
+  if constexpr (!LARGE) {
+    auto chain = [&](const nb_d2* av, const nb_d2* bv, int t)
+                     __attribute__((always_inline)) {
+      nb_d4 acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-    for (int it = 0; it < G_PAIRS; ++it) {
-      acc = MFMA(av[it].x, bv[it].x, acc);
-      acc = MFMA(av[it].y, bv[it].y, acc);
+      for (int it = 0; it < G_PAIRS; ++it) {
+        acc = MFMA(av[it].x, bv[it].x, acc);
+        acc = MFMA(av[it].y, bv[it].y, acc);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        red[((t * 4 + wave) * 4 + r) * 64 + lane] = acc[r];
+    };
+    chain(c0, c1, 0);
+    if (has[1]) chain(c0, cx, 1);
+    if (has[2]) chain(c2, c1, 2);
+    if (has[3]) {
+      if (three) chain(cx, c1, 3);
+      else chain(c2, cx, 3);
+    }
+  } else {
+    // every row tile of the minibatch, G_PAIRS pairs of each wavefront per
+    // round, the chains carried from round to round (each in the order of
+    // the small layout: row tiles wave / 2, wave / 2 + 2, ...)
+    const int n_rt = (nb + 15) >> 4;
+    nb_d4 acc[G_MAX_TILES];
+#pragma unroll
+    for (int t = 0; t < G_MAX_TILES; ++t) acc[t] = nb_d4{0.0, 0.0, 0.0, 0.0};
+    auto chain = [&](const nb_d2* av, const nb_d2* bv, nb_d4& c)
+                     __attribute__((always_inline)) {
+#pragma unroll
+      for (int it = 0; it < G_PAIRS; ++it) {
+        c = MFMA(av[it].x, bv[it].x, c);
+        c = MFMA(av[it].y, bv[it].y, c);
+      }
+    };
+    for (int it0 = 0; it0 < (n_rt + 1) >> 1; it0 += G_PAIRS) {
+      g_load_chunk(g.as, g.lda, kt0, wave, lane, it0, n_rt, c0);
+      g_load_chunk(g.bs, g.ldb, ht0, wave, lane, it0, n_rt, c1);
+      if (nk > 1) g_load_chunk(g.as, g.lda, kt0 + 1, wave, lane, it0, n_rt, c2);
+      if (three) g_load_chunk(g.as, g.lda, kt0 + 2, wave, lane, it0, n_rt, cx);
+      else if (nh > 1)
+        g_load_chunk(g.bs, g.ldb, ht0 + 1, wave, lane, it0, n_rt, cx);
+      chain(c0, c1, acc[0]);
+      if (has[1]) chain(c0, cx, acc[1]);
+      if (has[2]) chain(c2, c1, acc[2]);
+      if (has[3]) {
+        if (three) chain(cx, c1, acc[3]);
+        else chain(c2, cx, acc[3]);
+      }
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
-      red[((t * 4 + wave) * 4 + r) * 64 + lane] = acc[r];
-  };
-  chain(c0, c1, 0);
-  if (has[1]) chain(c0, cx, 1);
-  if (has[2]) chain(c2, c1, 2);
-  if (has[3]) {
-    if (three) chain(cx, c1, 3);
-    else chain(c2, cx, 3);
+    for (int t = 0; t < G_MAX_TILES; ++t)
+      if (has[t]) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          red[((t * 4 + wave) * 4 + r) * 64 + lane] = acc[t][r];
+      }
   }
   G_STAMP(31);
   lds_barrier();
@@ -1128,24 +1235,25 @@ __device__ __forceinline__ void g_job_shape(const TrainArgs& a,
   G_STAMP(32);
 }
 
-template <class Hook>
+template <bool LARGE, class Hook>
 __device__ __forceinline__ void g_job(const TrainArgs& a, const NetState& st,
                                       const GJob& jb, int nb, double lr_t,
                                       double* red, Hook&& first_loads,
                                       bool timed = false) {
   const int shape = jb.nk * 4 + jb.nh;           // (wave-uniform)
   if (shape == 2 * 4 + 1)
-    g_job_shape<2, 1>(a, st, jb, nb, lr_t, red, first_loads, timed);
+    g_job_shape<2, 1, LARGE>(a, st, jb, nb, lr_t, red, first_loads, timed);
   else if (shape == 1 * 4 + 2)
-    g_job_shape<1, 2>(a, st, jb, nb, lr_t, red, first_loads, timed);
+    g_job_shape<1, 2, LARGE>(a, st, jb, nb, lr_t, red, first_loads, timed);
   else if (shape == 3 * 4 + 1)
-    g_job_shape<3, 1>(a, st, jb, nb, lr_t, red, first_loads, timed);
+    g_job_shape<3, 1, LARGE>(a, st, jb, nb, lr_t, red, first_loads, timed);
   else if (shape == 2 * 4 + 2)
-    g_job_shape<2, 2>(a, st, jb, nb, lr_t, red, first_loads, timed);
+    g_job_shape<2, 2, LARGE>(a, st, jb, nb, lr_t, red, first_loads, timed);
   else
-    g_job_shape<1, 1>(a, st, jb, nb, lr_t, red, first_loads, timed);
+    g_job_shape<1, 1, LARGE>(a, st, jb, nb, lr_t, red, first_loads, timed);
 }
 
+template <bool LARGE>
 __global__ void __launch_bounds__(256)
 nb_train_g_kernel(TrainArgs a, int nb, long long t_adam) {
   __shared__ __attribute__((aligned(16))) double red[G_MAX_TILES * 1024];
@@ -1153,9 +1261,10 @@ nb_train_g_kernel(TrainArgs a, int nb, long long t_adam) {
   if (st.scal[4] != 0.0) return;                 // network already stopped
   // the first workgroup also folds the step's loss (the resident kernel gives
   // that to its least loaded workgroup)
-  if (blockIdx.x == 0 && threadIdx.x < 64) loss_fold(st, nb, (int)threadIdx.x);
-  g_job(a, st, g_job_record(a.jobs, (int)blockIdx.x), nb, adam_lr(a, t_adam), red,
-        []() {});
+  if (blockIdx.x == 0 && threadIdx.x < 64)
+    loss_fold<LARGE>(a, st, nb, (int)threadIdx.x);
+  g_job<LARGE>(a, st, g_job_record(a.jobs, (int)blockIdx.x), nb,
+               adam_lr(a, t_adam), red, []() {});
 }
 
 // end of epoch: loss curve and the stopping rule of _fit_stochastic
@@ -1395,7 +1504,7 @@ __device__ const int g_stamp_order[N_STAMPS] = {0, 1, 5, 33, 30, 31, 36, 32,
 // owned XCD a free slot, through which the workgroups of OTHER grids -- a
 // concurrent trainer's, which leave at once here, or any other kernel's --
 // pass while this one is resident)
-template <int KT1>
+template <int KT1, bool LARGE>
 __global__ void __launch_bounds__(256, 2)
 nb_train_xcd_kernel(TrainArgs a, FleetData fleet, XcdMap map, SyncTable tab,
                     int* sync) {
@@ -1456,7 +1565,7 @@ nb_train_xcd_kernel(TrainArgs a, FleetData fleet, XcdMap map, SyncTable tab,
   // read again in this step once every tile is past its delta-2 stage -- and a
   // LATE job, of layer 1, behind the barrier that ends FB.  Without it (two
   // networks per XCD): jobs slot, slot + slots, ... behind that barrier.
-  const bool use_sched = a.sched != nullptr && !two;
+  const bool use_sched = !LARGE && a.sched != nullptr && !two;
   int early_i = -1, late_i = slot < a.n_jobs ? slot : -1;
   if (use_sched) {
     early_i = __builtin_amdgcn_readfirstlane(a.sched[2 * slot]);
@@ -1542,8 +1651,17 @@ nb_train_xcd_kernel(TrainArgs a, FleetData fleet, XcdMap map, SyncTable tab,
       const int ep2 = last ? ep + 1 : ep;
       const long long start2 = last ? 0 : start + batch;
       const int nb2 = (int)((n - start2 < batch) ? (n - start2) : batch);
-      const bool next_rows = ep2 < a.n_epochs && slot * 16 < nb2;
-      if (slot * 16 < nb) {
+      // (LARGE: no prefetch -- a workgroup runs several row tiles)
+      const bool next_rows = !LARGE && ep2 < a.n_epochs && slot * 16 < nb2;
+      if (LARGE) {
+        // row tiles slot, slot + slots, ... of the minibatch (G contracts
+        // these only: nothing to clear past its end)
+        for (int tile = slot; tile * 16 < nb; tile += slots) {
+          fb_gather<KT1>(nd, a.n_dim, tile, nb,
+                         fb_row_index(nd, tile, ep, start, nb), rows);
+          fb_body<KT1, false, true>(a, st, net, tile, nb, rows, lds, []() {});
+        }
+      } else if (slot * 16 < nb) {
         if (!have_rows)
           fb_gather<KT1>(nd, a.n_dim, slot, nb,
                          fb_row_index(nd, slot, ep, start, nb), rows);
@@ -1551,7 +1669,7 @@ nb_train_xcd_kernel(TrainArgs a, FleetData fleet, XcdMap map, SyncTable tab,
         // where the rows themselves are fetched behind the barrier signal:
         // neither of the two dependent loads is waited for where it is issued
         if (next_rows) row_next = fb_row_index(nd, slot, ep2, start2, nb2);
-        fb_body<KT1, false>(a, st, net, slot, nb, rows, lds,
+        fb_body<KT1, false, false>(a, st, net, slot, nb, rows, lds,
                             [&]() __attribute__((always_inline)) {
                               if (lane == 0)
                                 __hip_atomic_fetch_add(
@@ -1605,7 +1723,8 @@ nb_train_xcd_kernel(TrainArgs a, FleetData fleet, XcdMap map, SyncTable tab,
             TR_STAMP(2);
             SLOT_STAMP(1);
             // the last workgroup folds the loss
-            if (slot == slots - 1 && wave == 3) loss_fold(st, nb, lane);
+            if (slot == slots - 1 && wave == 3)
+              loss_fold<LARGE>(a, st, nb, lane);
             past_fb = true;
           }
           if (job >= 0) {
@@ -1613,7 +1732,7 @@ nb_train_xcd_kernel(TrainArgs a, FleetData fleet, XcdMap map, SyncTable tab,
             const GJob jb = use_sched ? (early ? early_job : late_job)
                                       : (r == 0 ? late_job
                                                 : g_job_record(a.jobs, job));
-            g_job(a, st, jb, nb, lr_t, lds + FbLds<KT1>::G_RED,
+            g_job<LARGE>(a, st, jb, nb, lr_t, lds + FbLds<KT1>::G_RED,
                   [&]() __attribute__((always_inline)) {
                     if (past_fb && have_rows && !fetched) {
                       fb_gather<KT1>(nd, a.n_dim, slot, nb2, row_next, rows);
@@ -1952,6 +2071,13 @@ struct nb_trainer {
   int* jobs_dev = nullptr;         // job list of the G phase
   int* sched_dev = nullptr;        // (early, late) job per workgroup, or null
   int n_jobs = 0;
+  // minibatches above SMALL_BATCH rows: the stash of every network in an
+  // allocation of its own, laid out for `rowt` row tiles (nb_trainer_set_hparams)
+  bool large = false;
+  int rowt = G_ROWT;
+  double* big_stash = nullptr;
+  int big_rowt = 0;                // row tiles big_stash is laid out for
+  std::vector<nb_gd*> pool_stash;  // the stash of the small layout
   bool two_launch = false;         // fall back to two launches per step
   XcdMap xcd_map;                  // XCDs owned by this trainer's networks
   unsigned xcd_owned = 0;
@@ -2161,6 +2287,7 @@ int nb_trainer_create_fleet(int32_t n_dim, int32_t n_networks,
     s.W = (nb_gd*)base; s.M = s.W + t->n_w; s.V = s.M + t->n_w;
     s.WT = s.V + t->n_w;
     s.stash = s.WT + WT_DOUBLES;
+    t->pool_stash.push_back(s.stash);
     s.loss_curve = s.stash + stash;
     s.scal = s.loss_curve + curve;
     t->nets_host.push_back(s);
@@ -2220,10 +2347,47 @@ int nb_trainer_set_hparams(nb_trainer* t, double lr, double beta1,
                            double beta2, double epsilon, int32_t batch,
                            int32_t max_iter, int32_t n_iter_no_change,
                            double tol) {
-  if (batch < 1 || batch > 200 || max_iter < 1 || max_iter > 10000) {
-    nb_set_error("trainer: batch must be 1..200 and max_iter 1..10000");
+  if (batch < 1 || batch > NB_TRAIN_MAX_BATCH || max_iter < 1 ||
+      max_iter > 10000) {
+    nb_set_error("trainer: batch must be 1..%d and max_iter 1..10000",
+                 NB_TRAIN_MAX_BATCH);
     return NB_ERR_UNSUPPORTED;
   }
+  // The layout follows the largest minibatch any network sees (batch clipped
+  // to its rows, as scikit-learn does): up to SMALL_BATCH rows the stash in
+  // the pool (G_ROWT row tiles), beyond it one laid out for the batch, with
+  // the loss partials of its row tiles behind it.  A change of layout waits
+  // for the device (work still queued reads the network records).
+  long long eff = 0;
+  for (long long n : t->ns) eff = std::max(eff, std::min(n, (long long)batch));
+  const bool large = eff > SMALL_BATCH;
+  const int rowt = large ? (int)((eff + 15) / 16) : G_ROWT;
+  if (large != t->large || (large && rowt > t->big_rowt)) {
+    NB_HIP_CHECK(hipDeviceSynchronize());
+    if (large && rowt > t->big_rowt) {
+      if (t->big_stash) NB_HIP_CHECK(hipFree(t->big_stash));
+      t->big_stash = nullptr;
+      t->big_rowt = 0;
+      const long long per = (stash_doubles(16LL * rowt, 16 * t->kt1) + rowt +
+                             511) / 512 * 512;
+      const size_t bytes = (size_t)per * t->E * sizeof(double);
+      NB_HIP_CHECK(hipMalloc((void**)&t->big_stash, bytes));
+      // (finite contents: G scales the rows past a minibatch by zero)
+      NB_HIP_CHECK(hipMemset(t->big_stash, 0, bytes));
+      t->big_rowt = rowt;
+    }
+    const long long per = (stash_doubles(16LL * t->big_rowt, 16 * t->kt1) +
+                           t->big_rowt + 511) / 512 * 512;
+    for (int i = 0; i < t->E; ++i)
+      t->nets_host[i].stash = large ? (nb_gd*)(t->big_stash + (size_t)i * per)
+                                    : t->pool_stash[i];
+    NB_HIP_CHECK(hipMemcpy(t->nets_dev, t->nets_host.data(),
+                           t->E * sizeof(NetState), hipMemcpyHostToDevice));
+    t->large = large;
+  }
+  // (the stash holds big_rowt >= rowt row tiles: the kernels address it by
+  // the layout's count)
+  t->rowt = large ? t->big_rowt : G_ROWT;
   t->lr = lr; t->b1 = beta1; t->b2 = beta2; t->eps = epsilon;
   t->batch = batch; t->max_iter = max_iter;
   t->n_iter_no_change = n_iter_no_change; t->tol = tol;
@@ -2254,7 +2418,9 @@ int nb_trainer_run_fleet(nb_trainer* t, const int32_t* const* perm_dev_of,
   a.nets = t->nets_dev; a.X = (const nb_gd*)t->X; a.y = (const nb_gd*)t->y;
   a.perm = (const nb_gi*)perm_dev_of[0];
   a.jobs = (const nb_gi*)t->jobs_dev; a.n_jobs = t->n_jobs;
-  a.sched = (const nb_gi*)t->sched_dev;
+  // (LARGE: every workgroup has row tiles -- the jobs go behind the barrier)
+  a.sched = t->large ? nullptr : (const nb_gi*)t->sched_dev;
+  a.rowt = t->rowt;
   a.sched_jobs = a.sched ? a.sched + 2 * XCD_SLOTS : nullptr;
   a.n = t->n; a.n_dim = t->n_dim; a.kt1 = t->kt1; a.n_epochs = n_epochs;
   a.max_iter = t->max_iter; a.n_iter_no_change = t->n_iter_no_change;
@@ -2293,8 +2459,12 @@ int nb_trainer_run_fleet(nb_trainer* t, const int32_t* const* perm_dev_of,
     switch (t->kt1) {
 #define NB_CASE(KT1_)                                                      \
       case KT1_:                                                           \
-        hipLaunchKernelGGL(nb_train_xcd_kernel<KT1_>, grid, blk, 0, s, a,  \
-                           fleet, t->xcd_map, tab, t->sync_dev);           \
+        if (t->large)                                                      \
+          hipLaunchKernelGGL((nb_train_xcd_kernel<KT1_, true>), grid, blk, \
+                             0, s, a, fleet, t->xcd_map, tab, t->sync_dev); \
+        else                                                               \
+          hipLaunchKernelGGL((nb_train_xcd_kernel<KT1_, false>), grid, blk,\
+                             0, s, a, fleet, t->xcd_map, tab, t->sync_dev); \
         break;
       NB_CASE(1) NB_CASE(2) NB_CASE(3) NB_CASE(4) NB_CASE(5)
       NB_CASE(6) NB_CASE(7) NB_CASE(8) NB_CASE(9)
@@ -2319,21 +2489,31 @@ int nb_trainer_run_fleet(nb_trainer* t, const int32_t* const* perm_dev_of,
       const long long start = (long long)sidx * a.batch;
       const int nb = (int)((n - start < a.batch) ? (n - start) : a.batch);
       // (all G_ROWT row tiles: the ones past the end of a short minibatch
-      // clear their delta rows)
-      const dim3 gfb(G_ROWT, t->E), gg(t->n_jobs, t->E), blk(256);
+      // clear their delta rows; LARGE: the row tiles of the minibatch)
+      const dim3 gfb(t->large ? (nb + 15) / 16 : G_ROWT, t->E),
+          gg(t->n_jobs, t->E), blk(256);
       t->t_adam += 1;
       switch (t->kt1) {
 #define NB_CASE(KT1_)                                                      \
         case KT1_:                                                         \
-          hipLaunchKernelGGL(nb_train_fb_kernel<KT1_>, gfb, blk, 0, s, a,  \
-                             ep, start, nb);                               \
+          if (t->large)                                                    \
+            hipLaunchKernelGGL((nb_train_fb_kernel<KT1_, true>), gfb, blk, \
+                               0, s, a, ep, start, nb);                    \
+          else                                                             \
+            hipLaunchKernelGGL((nb_train_fb_kernel<KT1_, false>), gfb, blk,\
+                               0, s, a, ep, start, nb);                    \
           break;
         NB_CASE(1) NB_CASE(2) NB_CASE(3) NB_CASE(4) NB_CASE(5)
         NB_CASE(6) NB_CASE(7) NB_CASE(8) NB_CASE(9)
 #undef NB_CASE
         default: nb_set_error("n_dim unsupported"); return NB_ERR_UNSUPPORTED;
       }
-      hipLaunchKernelGGL(nb_train_g_kernel, gg, blk, 0, s, a, nb, t->t_adam);
+      if (t->large)
+        hipLaunchKernelGGL(nb_train_g_kernel<true>, gg, blk, 0, s, a, nb,
+                           t->t_adam);
+      else
+        hipLaunchKernelGGL(nb_train_g_kernel<false>, gg, blk, 0, s, a, nb,
+                           t->t_adam);
     }
     hipLaunchKernelGGL(nb_train_epoch_kernel, dim3(t->E), dim3(64), 0, s, a,
                        t->t_adam);
@@ -2484,6 +2664,7 @@ int nb_dbg_train_times(long long* out) {
 int nb_trainer_destroy(nb_trainer* t) {
   if (t == nullptr) return NB_OK;
   if (t->block_alloc) (void)hipFree(t->block_alloc);
+  if (t->big_stash) (void)hipFree(t->big_stash);
   g_xcd_in_use &= ~t->xcd_owned;
   if (t->pin_scal) (void)hipHostFree(t->pin_scal);
   if (t->pin_sync) (void)hipHostFree(t->pin_sync);

@@ -13,6 +13,7 @@ arithmetic (forward, backprop, Adam) runs in ``nb_mlp_train.hip``.
 """
 
 import ctypes as C
+import numbers
 import warnings
 
 import numpy as np
@@ -24,6 +25,8 @@ HIDDEN = (100, 50, 20)
 EPOCH_CHUNK = 16     # epochs per kernel launch (host prepares the next chunk
                      # of shuffles while the GPU trains)
 CHUNK_BYTES = 32 << 20   # ... fewer where a chunk's orders would exceed this
+MAX_BATCH = 4096     # largest minibatch of the device trainer
+                     # (NB_TRAIN_MAX_BATCH, include/nautilus_hip.h)
 
 
 class Network:
@@ -248,6 +251,8 @@ def _hparams_from_kwargs(kwargs):
         if key == 'random_state':
             warnings.warn("The 'random_state' keyword argument passed to the"
                           " neural network is ignored.", Warning, stacklevel=3)
+        elif key == 'batch_size':
+            hp['batch'] = _check_batch_size(val)
         elif key in known:
             hp[known[key]] = val
         elif key == 'hidden_layer_sizes':
@@ -262,6 +267,31 @@ def _hparams_from_kwargs(kwargs):
             raise ValueError(
                 'MLPRegressor option %r is not supported on the device' % key)
     return hp
+
+
+def _check_batch_size(val):
+    """scikit-learn's rule for ``batch_size`` (an integer >= 1 or 'auto',
+    which means min(200, n)) with the device trainer's cap on top; the clip
+    to the rows of a training set happens where they are known
+    (``_warn_batch_clip``, and the trainer clips on the device)."""
+    if isinstance(val, str) and val == 'auto':
+        return 200
+    if (isinstance(val, numbers.Integral)
+            and not isinstance(val, (bool, np.bool_))
+            and 1 <= val <= MAX_BATCH):
+        return int(val)
+    raise ValueError(
+        "batch_size must be 'auto' or an integer from 1 to %d (the largest "
+        "minibatch the device trainer holds); got %r" % (MAX_BATCH, val))
+
+
+def _warn_batch_clip(kwargs, n):
+    """scikit-learn's warning (_multilayer_perceptron.py:690-694) when an
+    integer batch_size exceeds the ``n`` rows of a training set."""
+    val = dict(kwargs).get('batch_size', 'auto')
+    if not isinstance(val, str) and val > n:
+        warnings.warn('Got `batch_size` less than 1 or larger than sample '
+                      'size. It is going to be clipped', stacklevel=4)
 
 
 def check_network_kwargs(kwargs):
@@ -308,6 +338,7 @@ class NeuralNetworkEmulator:
             emu.scale = scale.cpu().numpy()
             emu._dev = None
             emus.append(emu)
+            _warn_batch_clip(neural_network_kwargs, xs.shape[0])
             jobs.append(dict(xs=xs, y=yt, seeds=list(range(n_networks)),
                              hparams=hp))
         results = (train_ensembles(jobs) if comm is None or comm.world == 1
