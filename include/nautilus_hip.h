@@ -376,6 +376,36 @@ int nb_prior_transform(const double* u_dev, int64_t n, int32_t n_dim,
                        const uint8_t* kind, const double* loc,
                        const double* scale, double* out_dev, void* stream);
 
+/* The same transform for six families, table-driven, with fixed and tied
+ * parameters (prior.py:85-120 and the dictionary of prior.py:122-162).
+ * kind: 0 uniform, 1 norm, 2 loguniform / reciprocal (shapes a, b),
+ * 3 lognorm (shape s), 4 halfnorm, 5 truncnorm (shapes a, b); loc / scale /
+ * shape0 / shape1 are host arrays of length n_dim (scipy's arguments; unused
+ * shapes are ignored).  The prior has n_keys keys in order: key_column[k] is
+ * the column of the free parameter that key k is (or is tied to), or -1 for
+ * a fixed parameter with the constant key_value[k].  The table is uploaded
+ * once, here; nb_prior_table_transform only launches, on the caller's stream
+ * (one table serves any number of streams).  layout NB_PRIOR_ROW_MAJOR:
+ * out_dev is (n, n_dim) like u_dev.  NB_PRIOR_COLUMN_MAJOR: out_dev is
+ * (n_keys, n), one contiguous row per key.  A truncnorm whose interval
+ * starts more than NB_PRIOR_LOG_SPACE standard deviations from the mean (its
+ * mass underflows in double precision) is evaluated in log space; beyond
+ * NB_PRIOR_TRUNCNORM_MAX it is NB_ERR_UNSUPPORTED.                           */
+typedef struct nb_prior_table nb_prior_table;
+#define NB_PRIOR_ROW_MAJOR 0
+#define NB_PRIOR_COLUMN_MAJOR 1
+#define NB_PRIOR_LOG_SPACE 35.0
+#define NB_PRIOR_TRUNCNORM_MAX 1e150
+int nb_prior_table_create(int32_t n_dim, const uint8_t* kind,
+                          const double* loc, const double* scale,
+                          const double* shape0, const double* shape1,
+                          int32_t n_keys, const int32_t* key_column,
+                          const double* key_value, nb_prior_table** out);
+int nb_prior_table_destroy(nb_prior_table* table);
+int nb_prior_table_transform(const nb_prior_table* table, const double* u_dev,
+                             int64_t n, int32_t layout, double* out_dev,
+                             void* stream);
+
 /* Device likelihoods of the benchmark problems (the user-side callable of
  * sampler.py:863-873 for the BASELINE configurations C3 and C5; Gaussians go
  * through nb_neural_score): out_dev[i] = log L of row i of u_dev (unit-cube

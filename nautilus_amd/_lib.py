@@ -140,6 +140,13 @@ _SIGNATURES = {
     'nb_prior_transform': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32,
                                      C.c_void_p, c_double_p, c_double_p,
                                      C.c_void_p, C.c_void_p]),
+    'nb_prior_table_create': (C.c_int, [C.c_int32, C.c_void_p, c_double_p,
+                                        c_double_p, c_double_p, c_double_p,
+                                        C.c_int32, c_int32_p, c_double_p,
+                                        C.POINTER(C.c_void_p)]),
+    'nb_prior_table_destroy': (C.c_int, [C.c_void_p]),
+    'nb_prior_table_transform': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64,
+                                           C.c_int32, C.c_void_p, C.c_void_p]),
     'nb_loglike_rosenbrock': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32,
                                         C.c_double, C.c_double, C.c_double,
                                         C.c_void_p, C.c_void_p]),

@@ -97,6 +97,11 @@ int nb_launch_standardize(const double* x, long long n, int d, double* mean,
 int nb_launch_prior(const double* u, long long n, int d,
                     const unsigned char* kind, const double* loc,
                     const double* scale, double* out, hipStream_t stream);
+int nb_launch_prior_table(const double* u, long long n, int d,
+                          const double* par, const unsigned char* kind,
+                          int n_keys, const int* key_column,
+                          const double* key_value, int column_major,
+                          int level, double* out, hipStream_t stream);
 long long nb_gmm_out_stride_impl(int d);
 long long nb_gmm_scratch_stride_impl(long long n, int d);
 long long nb_gmm_work_doubles_impl(long long n, int d, int n_init);
@@ -1055,6 +1060,208 @@ int nb_prior_transform(const double* u, int64_t n, int32_t n_dim,
       return NB_ERR_UNSUPPORTED;
     }
   return nb_launch_prior(u, n, n_dim, kind, loc, scale, out, as_stream(stream));
+}
+
+// Device-resident table of a prior (nb_transform.hip, PT_* rows): one
+// allocation holding par[NB_PRIOR_NPAR][n_dim], key_value[n_keys], key_column[n_keys] and
+// kind[n_dim], in that order (doubles first, so everything is aligned).
+struct nb_prior_table {
+  double* dev = nullptr;
+  int n_dim = 0, n_keys = 0;
+  int level = 0;            // kernel variant: 0 kinds 0 and 2 only, 1 with the
+                            // normal families, 2 with log-space truncnorm
+  const double* par() const { return dev; }
+  const double* key_value() const { return dev + NB_PRIOR_NPAR * (size_t)n_dim; }
+  const int* key_column() const { return (const int*)(key_value() + n_keys); }
+  const unsigned char* kind() const {
+    return (const unsigned char*)(key_column() + n_keys);
+  }
+};
+
+namespace {
+
+// Phi(x) in extended precision; exact in the lower tail, where it is used
+long double pt_phi(double x) {
+  return 0.5L * erfcl(-(long double)x / sqrtl(2.0L));
+}
+
+// the constants of pt_truncnorm: Phi(a), 1 - Phi(b) and the mass between,
+// each from the tail it lives in
+void pt_truncnorm_constants(double a, double b, double* out3) {
+  const long double cdf_a = pt_phi(a), sf_b = pt_phi(-b);
+  long double mass;
+  if (a > 0.0) {
+    mass = pt_phi(-a) - sf_b;
+  } else if (b < 0.0) {
+    mass = pt_phi(b) - cdf_a;
+  } else {                                  // straddles 0: two positive terms
+    mass = 0.5L * (erfl((long double)b / sqrtl(2.0L)) +
+                   erfl(-(long double)a / sqrtl(2.0L)));
+  }
+  out3[0] = (double)cdf_a;
+  out3[1] = (double)sf_b;
+  out3[2] = (double)mass;
+}
+
+// log erfcx(x / sqrt 2) for x >= NB_PRIOR_LOG_SPACE from the asymptotic series
+// erfcx(y) = 1 / (y sqrt pi) sum_k (-1)^k (2k - 1)!! / (2 y^2)^k, whose terms
+// fall by 2 y^2 / (2k + 1) > 600 each there
+long double pt_log_erfcx_tail(double x) {
+  const long double y = (long double)x / sqrtl(2.0L);
+  long double term = 1.0L, sum = 1.0L;
+  for (int k = 1; k <= 12; ++k) {
+    term *= -(long double)(2 * k - 1) / (2.0L * y * y);
+    sum += term;
+  }
+  return logl(sum) - logl(y) - 0.5L * logl(acosl(-1.0L));
+}
+
+// the constants of pt_truncnorm_log for [a, b], a >= NB_PRIOR_LOG_SPACE
+void pt_truncnorm_log_constants(double a, double b, double* out3) {
+  const long double log_ea = pt_log_erfcx_tail(a);
+  long double r0 = 0.0L, r1 = 1.0L;
+  if (std::isfinite(b)) {
+    const long double log_r0 = pt_log_erfcx_tail(b) - log_ea -
+        0.5L * ((long double)b - a) * ((long double)b + a);
+    r0 = expl(log_r0);
+    r1 = -expm1l(log_r0);
+  }
+  out3[0] = (double)log_ea;
+  out3[1] = (double)r0;
+  out3[2] = (double)r1;
+}
+
+}  // namespace
+
+int nb_prior_table_create(int32_t n_dim, const uint8_t* kind,
+                          const double* loc, const double* scale,
+                          const double* shape0, const double* shape1,
+                          int32_t n_keys, const int32_t* key_column,
+                          const double* key_value, nb_prior_table** out) {
+  if (out == nullptr || n_dim < 1 || n_dim > 16 * NB_MAX_DT || n_keys < 1 ||
+      kind == nullptr || loc == nullptr || scale == nullptr ||
+      shape0 == nullptr || shape1 == nullptr || key_column == nullptr ||
+      key_value == nullptr) {
+    nb_set_error("bad prior table arguments");
+    return NB_ERR_ARG;
+  }
+  *out = nullptr;
+  const size_t d = (size_t)n_dim;
+  std::vector<double> par(NB_PRIOR_NPAR * d, 0.0);
+  std::vector<unsigned char> kind_dev(kind, kind + d);
+  for (int j = 0; j < n_dim; ++j) {
+    const double a = shape0[j], b = shape1[j];
+    if (kind[j] > 5) {
+      nb_set_error("prior kind %d of parameter %d is not supported", kind[j], j);
+      return NB_ERR_UNSUPPORTED;
+    }
+    if (!std::isfinite(loc[j]) || !(scale[j] > 0.0) ||
+        !std::isfinite(scale[j])) {
+      nb_set_error("parameter %d: loc must be finite and scale positive", j);
+      return NB_ERR_ARG;
+    }
+    par[0 * d + j] = loc[j];
+    par[1 * d + j] = scale[j];
+    if (kind[j] == 2) {
+      if (!(a > 0.0) || !(a < b) || !std::isfinite(b)) {
+        nb_set_error("parameter %d: log-uniform needs 0 < a < b < inf", j);
+        return NB_ERR_ARG;
+      }
+      par[2 * d + j] = std::log(a);
+      par[3 * d + j] = std::log(b) - std::log(a);
+    } else if (kind[j] == 3) {
+      if (!(a > 0.0) || !std::isfinite(a)) {
+        nb_set_error("parameter %d: log-normal needs a shape s > 0", j);
+        return NB_ERR_ARG;
+      }
+      par[2 * d + j] = a;
+    } else if (kind[j] == 5) {
+      if (!(a < b)) {
+        nb_set_error("parameter %d: truncated normal needs a < b", j);
+        return NB_ERR_ARG;
+      }
+      if (a > NB_PRIOR_TRUNCNORM_MAX || b < -NB_PRIOR_TRUNCNORM_MAX) {
+        nb_set_error("parameter %d: a truncated normal whose interval lies "
+                     "more than %g standard deviations from the mean is not "
+                     "supported", j, (double)NB_PRIOR_TRUNCNORM_MAX);
+        return NB_ERR_UNSUPPORTED;
+      }
+      double c3[3];
+      if (a > NB_PRIOR_LOG_SPACE || b < -NB_PRIOR_LOG_SPACE) {
+        // far tail: kind 6 on the interval mirrored to the right
+        const double sign = a > 0.0 ? 1.0 : -1.0;
+        const double lo = a > 0.0 ? a : -b, hi = a > 0.0 ? b : -a;
+        kind_dev[j] = 6;
+        par[2 * d + j] = lo;
+        par[3 * d + j] = hi;
+        pt_truncnorm_log_constants(lo, hi, c3);
+        par[7 * d + j] = sign;
+      } else {
+        par[2 * d + j] = a;
+        par[3 * d + j] = b;
+        pt_truncnorm_constants(a, b, c3);
+      }
+      for (int t = 0; t < 3; ++t) par[(4 + t) * d + j] = c3[t];
+    }
+  }
+  for (int k = 0; k < n_keys; ++k)
+    if (key_column[k] < -1 || key_column[k] >= n_dim) {
+      nb_set_error("key %d refers to column %d of %d", k, key_column[k], n_dim);
+      return NB_ERR_ARG;
+    }
+  const size_t bytes = (NB_PRIOR_NPAR * d + (size_t)n_keys) * sizeof(double) +
+                       (size_t)n_keys * sizeof(int) + d;
+  std::vector<unsigned char> host(bytes);
+  unsigned char* at = host.data();
+  std::memcpy(at, par.data(), NB_PRIOR_NPAR * d * sizeof(double));
+  at += NB_PRIOR_NPAR * d * sizeof(double);
+  std::memcpy(at, key_value, (size_t)n_keys * sizeof(double));
+  at += (size_t)n_keys * sizeof(double);
+  std::memcpy(at, key_column, (size_t)n_keys * sizeof(int));
+  at += (size_t)n_keys * sizeof(int);
+  std::memcpy(at, kind_dev.data(), d);
+  nb_prior_table* t = new nb_prior_table;
+  t->n_dim = n_dim;
+  t->n_keys = n_keys;
+  for (int j = 0; j < n_dim; ++j) {
+    const int need = kind_dev[j] == 6 ? 2 : (kind[j] != 0 && kind[j] != 2);
+    if (need > t->level) t->level = need;
+  }
+  hipError_t e = hipMalloc((void**)&t->dev, bytes);
+  if (e == hipSuccess)
+    e = hipMemcpy(t->dev, host.data(), bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    nb_set_error("prior table upload failed: %s", hipGetErrorString(e));
+    if (t->dev != nullptr) (void)hipFree(t->dev);
+    delete t;
+    return NB_ERR_HIP;
+  }
+  *out = t;
+  return NB_OK;
+}
+
+int nb_prior_table_destroy(nb_prior_table* table) {
+  if (table == nullptr) return NB_OK;
+  (void)hipFree(table->dev);
+  delete table;
+  return NB_OK;
+}
+
+int nb_prior_table_transform(const nb_prior_table* table, const double* u,
+                             int64_t n, int32_t layout, double* out,
+                             void* stream) {
+  if (table == nullptr || (layout != NB_PRIOR_ROW_MAJOR &&
+                           layout != NB_PRIOR_COLUMN_MAJOR) ||
+      n < 0 || (n > 0 && (u == nullptr || out == nullptr))) {
+    nb_set_error("bad prior transform arguments");
+    return NB_ERR_ARG;
+  }
+  return nb_launch_prior_table(u, n, table->n_dim, table->par(), table->kind(),
+                               table->n_keys, table->key_column(),
+                               table->key_value(),
+                               layout == NB_PRIOR_COLUMN_MAJOR, table->level,
+                               out,
+                               as_stream(stream));
 }
 
 int nb_loglike_rosenbrock(const double* u, int64_t n, int32_t n_dim, double lo,

@@ -16,6 +16,7 @@
 #define NB_HT2 4
 #define NB_HT3 2
 #define NB_TILE 256          // doubles in one 16x16 tile
+#define NB_PRIOR_NPAR 8      // rows of a prior table (nb_transform.hip, PT_*)
 
 typedef double nb_d4 __attribute__((ext_vector_type(4)));
 // a pair of doubles at an 8-byte-aligned address: one 16-byte load

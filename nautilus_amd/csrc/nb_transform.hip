@@ -101,6 +101,204 @@ nb_prior_kernel(const double* __restrict__ u, long long total, int d,
   }
 }
 
+
+// Table-driven prior transform: the same x_j = dist_j.isf(1 - u_j) for six
+// families, with the per-column table in device memory (uploaded once per
+// prior by nb_prior_table_create, nb_api.hip) instead of a by-value argument.
+//   kind  scipy name             z(q), then x = z * scale + loc
+//   0     uniform                1 - q
+//   1     norm                   -ndtri(q)
+//   2     loguniform/reciprocal  exp(log a + (1 - q) (log b - log a))
+//   3     lognorm                exp(-s ndtri(q))
+//   4     halfnorm               -ndtri(q / 2)
+//   5     truncnorm              see pt_value (and pt_truncnorm_log)
+// Products and sums are rounded one by one (no contraction), as numpy does,
+// so that kind 0 equals scipy bit for bit whatever loc and scale are.
+//
+// A workgroup stages PT_ROWS rows in LDS with 16-byte reads that run along
+// the rows; then every wavefront takes whole columns (lane = row), so a
+// wavefront executes ONE kind and the ndtri families do not pay for each
+// other.  The LDS row stride is odd in doubles: the row-wise fill writes
+// consecutive doubles, the column-wise pass reads addresses 2 * LS dwords
+// apart, which fall on 32 distinct even banks per half wavefront.  From the
+// staged block either layout is written: row-major (n, d), or column-major
+// (n_keys, n) with one contiguous row per key of the prior -- a free
+// parameter's column, a fixed parameter's constant, a tied parameter's root
+// column written a second time.
+constexpr int PT_ROWS = 64;
+constexpr int PT_THREADS = 256;
+// rows of the parameter table (column-contiguous: par[row * d + column])
+enum { PT_LOC = 0, PT_SCALE, PT_P0, PT_P1, PT_P2, PT_P3, PT_P4, PT_P5, PT_NPAR };
+static_assert(PT_NPAR == NB_PRIOR_NPAR, "table rows");
+
+// Standard normal truncated to [a, b] (kind 5): with p = 1 - q (exact for
+// every q that is 1 - u rounded once),
+//   Phi(x) = Phi(a) + p M      1 - Phi(x) = (1 - Phi(b)) + q M
+// where M = Phi(b) - Phi(a) is the mass of the interval.  Both are sums of
+// positive terms, so neither cancels; the one that is at most 1/2 is inverted
+// (the tail side of x: there ndtri turns a relative error delta of its
+// argument into at most 1.26 delta in x, while on the far side it amplifies
+// by 1 / pdf).  The three constants come from the host in extended precision
+// (each from the tail it lives in), one fma rounds a function that is
+// monotone in u once, and the choice of side is monotone as well, so the
+// result is non-decreasing in u; the clamp keeps it inside [a, b].
+//
+// Kind 6 (internal; nb_prior_table_create turns a truncnorm into it when the
+// interval starts more than NB_PRIOR_LOG_SPACE standard deviations out, where
+// the masses above underflow): the same equation in log space.  With the
+// interval mirrored to the right tail, [a, b] with a > 0, and S = 1 - Phi,
+//   S(x) / S(a) = r = R0 + qq R1,   R0 = S(b) / S(a),  R1 = 1 - R0
+// (qq = q, or p for a mirrored interval), and with S(x) = erfcx(x / sqrt 2)
+// exp(-x^2 / 2) / 2 the equation log S(x) - log S(a) - log r = 0 reads
+//   log erfcx(x / sqrt 2) - log erfcx(a / sqrt 2) - (x - a)(x + a) / 2 - log r
+// in which no term is large.  Newton steps from the asymptotic solution
+// x^2 = a^2 - 2 log r; the derivative is minus the hazard rate
+// sqrt(2 / pi) / erfcx(x / sqrt 2).  (An "ndtri of a logarithm" without
+// forming the logarithm of the tiny mass at all.)
+__device__ __forceinline__ double pt_truncnorm_log(double qq, double a,
+                                                   double b, double log_ea,
+                                                   double r0, double r1) {
+  const double r = fma(qq, r1, r0);
+  const double lr = log(r);
+  double x = sqrt(fma(a, a, -2.0 * lr));
+#pragma unroll 1
+  for (int it = 0; it < 4; ++it) {
+    const double e = erfcx(x * 0.70710678118654752440);
+    const double f = (log(e) - log_ea) - 0.5 * (x - a) * (x + a) - lr;
+    x = fma(f * e, 1.2533141373155002512, x);         // sqrt(pi / 2)
+  }
+  x = r > 0.0 ? x : b;                    // all of the mass is below: x = b
+  return fmin(fmax(x, a), b);
+}
+
+// pt_value has ONE call site of normcdfinv and one of exp (the kinds differ
+// in the argument and in what is done with the result).  The library's
+// inverse normal distribution function alone takes more than 400 vector
+// registers, which leaves one wavefront per SIMD.  So the kernel comes in
+// three levels, chosen per table: 0 for kinds 0 and 2 only (44 registers:
+// flat and log-uniform priors stream at full occupancy), 1 with the normal
+// families, 2 with the log-space truncnorm as well (its erfcx / log loop costs
+// the others a few per cent when it is compiled in).
+template <int LEVEL>
+__device__ __forceinline__ double pt_value(int kind, double u,
+                                           const double* __restrict__ par,
+                                           int d) {
+#pragma clang fp contract(off)
+  const double q = 1.0 - u;
+  const double p = 1.0 - q;
+  double z = p;                                       // kind 0
+  bool upper = false;
+  if (LEVEL >= 1 && (kind == 1 || (kind >= 3 && kind <= 5))) {
+    double arg = q;                                   // kinds 1, 3
+    if (kind == 4) arg = q * 0.5;
+    if (kind == 5) {
+      arg = fma(p, par[PT_P4 * d], par[PT_P2 * d]);   // Phi(x)
+      upper = arg > 0.5;
+      if (upper) arg = fma(q, par[PT_P4 * d], par[PT_P3 * d]);
+    }
+    z = normcdfinv(arg);
+    if (kind == 5) {
+      z = upper ? fmax(-z, 0.0) : z;
+      z = fmin(fmax(z, par[PT_P0 * d]), par[PT_P1 * d]);
+    } else if (kind != 3) {
+      z = -z;
+    }
+  }
+  if (kind == 2 || kind == 3) {
+    double t;
+    if (kind == 2) {
+      t = p * par[PT_P1 * d];
+      t = par[PT_P0 * d] + t;
+    } else {
+      t = par[PT_P0 * d] * z;
+      t = -t;
+    }
+    z = exp(t);
+  }
+  if (LEVEL >= 2 && kind == 6) {
+    const double sign = par[PT_P5 * d];
+    z = sign * pt_truncnorm_log(sign < 0.0 ? p : q, par[PT_P0 * d],
+                                par[PT_P1 * d], par[PT_P2 * d], par[PT_P3 * d],
+                                par[PT_P4 * d]);
+  }
+  const double zs = z * par[PT_SCALE * d];
+  return zs + par[PT_LOC * d];
+}
+
+// copies `total` doubles between a contiguous global span and the staged
+// block (row stride ls), two per lane and step; TO_LDS selects the direction
+template <bool TO_LDS>
+__device__ inline void pt_copy_block(double* __restrict__ g, double* lds,
+                                     int total, int d, int ls) {
+  const int pairs = total >> 1;
+  const int step_r = (2 * PT_THREADS) / d, step_c = (2 * PT_THREADS) % d;
+  int e = 2 * (int)threadIdx.x;
+  int r = e / d, c = e - r * d;
+  for (int i = threadIdx.x; i < pairs; i += PT_THREADS) {
+    const int r1 = c + 1 == d ? r + 1 : r;
+    const int c1 = c + 1 == d ? 0 : c + 1;
+    if (TO_LDS) {
+      const nb_d2u v = ((const nb_d2u*)g)[i];
+      lds[r * ls + c] = v.x;
+      lds[r1 * ls + c1] = v.y;
+    } else {
+      nb_d2u v;
+      v.x = lds[r * ls + c];
+      v.y = lds[r1 * ls + c1];
+      ((nb_d2u*)g)[i] = v;
+    }
+    r += step_r;
+    c += step_c;
+    if (c >= d) { c -= d; ++r; }
+  }
+  if ((total & 1) && threadIdx.x == 0) {    // last element of an odd block
+    const int rl = (total - 1) / d, cl = (total - 1) - rl * d;
+    if (TO_LDS) lds[rl * ls + cl] = g[total - 1];
+    else g[total - 1] = lds[rl * ls + cl];
+  }
+}
+
+template <bool COLUMN_MAJOR, int LEVEL>
+__global__ void __launch_bounds__(PT_THREADS)
+nb_prior_table_kernel(const double* __restrict__ u, long long n, int d, int ls,
+                      const double* __restrict__ par,
+                      const unsigned char* __restrict__ kind,
+                      int n_keys, const int* __restrict__ key_column,
+                      const double* __restrict__ key_value,
+                      double* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) double pt_lds[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long long n_blocks = (n + PT_ROWS - 1) / PT_ROWS;
+  for (long long blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
+    const long long row0 = blk * PT_ROWS;
+    const int rows = n - row0 < PT_ROWS ? (int)(n - row0) : PT_ROWS;
+    pt_copy_block<true>(const_cast<double*>(u) + row0 * d, pt_lds, rows * d, d,
+                        ls);
+    __syncthreads();
+    if (lane < rows) {
+      for (int col = wave; col < d; col += PT_THREADS / 64) {
+        double* at = pt_lds + lane * ls + col;
+        // the column, hence its kind, is the wavefront's: a scalar branch
+        const int kd = __builtin_amdgcn_readfirstlane((int)kind[col]);
+        *at = pt_value<LEVEL>(kd, *at, par + col, d);
+      }
+    }
+    __syncthreads();
+    if (COLUMN_MAJOR) {
+      for (int k = wave; k < n_keys; k += PT_THREADS / 64) {
+        const int col = key_column[k];
+        if (lane < rows)
+          out[(long long)k * n + row0 + lane] =
+              col >= 0 ? pt_lds[lane * ls + col] : key_value[k];
+      }
+    } else {
+      pt_copy_block<false>(out + row0 * d, pt_lds, rows * d, d, ls);
+    }
+    __syncthreads();
+  }
+}
+
 }  // namespace
 
 int nb_launch_prior(const double* u, long long n, int d,
@@ -118,6 +316,48 @@ int nb_launch_prior(const double* u, long long n, int d,
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(nb_prior_kernel, dim3((unsigned)blocks), dim3(256), 0,
                      stream, u, total, d, a, out);
+  NB_HIP_CHECK(hipGetLastError());
+  return NB_OK;
+}
+
+int nb_launch_prior_table(const double* u, long long n, int d,
+                          const double* par, const unsigned char* kind,
+                          int n_keys, const int* key_column,
+                          const double* key_value, int column_major,
+                          int level, double* out, hipStream_t stream) {
+  if (n <= 0) return NB_OK;
+  const int ls = d | 1;
+  const size_t lds = (size_t)PT_ROWS * ls * sizeof(double);
+  typedef void (*kernel_t)(const double*, long long, int, int, const double*,
+                           const unsigned char*, int, const int*,
+                           const double*, double*);
+  static const kernel_t kernels[6] = {
+      nb_prior_table_kernel<false, 0>, nb_prior_table_kernel<false, 1>,
+      nb_prior_table_kernel<false, 2>, nb_prior_table_kernel<true, 0>,
+      nb_prior_table_kernel<true, 1>, nb_prior_table_kernel<true, 2>};
+  if (level < 0 || level > 2) {
+    nb_set_error("bad prior table level %d", level);
+    return NB_ERR_ARG;
+  }
+  const int which = 3 * (column_major != 0) + level;
+  static size_t allowed[6] = {0, 0, 0, 0, 0, 0};
+  if (lds > allowed[which]) {
+    const hipError_t e = hipFuncSetAttribute(
+        (const void*)kernels[which],
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) {
+      nb_set_error("hipFuncSetAttribute(%zu bytes LDS) failed: %s", lds,
+                   hipGetErrorString(e));
+      return NB_ERR_HIP;
+    }
+    allowed[which] = lds;
+  }
+  long long blocks = (n + PT_ROWS - 1) / PT_ROWS;
+  if (blocks > 2048) blocks = 2048;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(kernels[which], dim3((unsigned)blocks), dim3(PT_THREADS),
+                     lds, stream, u, n, d, ls, par, kind, n_keys, key_column,
+                     key_value, out);
   NB_HIP_CHECK(hipGetLastError());
   return NB_OK;
 }

@@ -534,6 +534,55 @@ def prior_transform(u, kind, loc, scale):
 
 
 
+ROW_MAJOR, COLUMN_MAJOR = 0, 1          # NB_PRIOR_* of include/nautilus_hip.h
+
+
+class PriorTable:
+    """Device-resident table of a prior (``nb_prior_table_create``): kind,
+    loc, scale and two shapes per free parameter, and for every key of the
+    prior the column it shows (its own, or its root's for a tied parameter)
+    or -1 with the constant of a fixed parameter.  Uploaded once; every
+    ``transform`` is one launch on the current stream."""
+
+    def __init__(self, kind, loc, scale, shape0, shape1, key_column,
+                 key_value):
+        self._lib = lib = _lib.load()
+        kind = np.ascontiguousarray(kind, dtype=np.uint8)
+        arrays = [_f64(a) for a in (loc, scale, shape0, shape1)]
+        key_column = np.ascontiguousarray(key_column, dtype=np.int32)
+        key_value = _f64(key_value)
+        self.n_dim, self.n_keys = len(kind), len(key_column)
+        if any(len(a) != self.n_dim for a in arrays) or \
+                len(key_value) != self.n_keys:
+            raise ValueError('prior table arrays differ in length')
+        h = C.c_void_p()
+        _lib.check(lib.nb_prior_table_create(
+            self.n_dim, kind.ctypes.data_as(C.c_void_p),
+            *[_dp(a) for a in arrays], self.n_keys,
+            key_column.ctypes.data_as(_lib.c_int32_p), _dp(key_value),
+            C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, '_h', None)
+        if h:
+            self._lib.nb_prior_table_destroy(h)
+            self._h = None
+
+    def transform(self, u, layout=ROW_MAJOR):
+        """x = dist.isf(1 - u) (reference prior.py:85-120) of the rows of a
+        cuda tensor: (n, n_dim) for ROW_MAJOR, (n_keys, n) -- one contiguous
+        row per key of the prior -- for COLUMN_MAJOR."""
+        u = as_device_points(u, self.n_dim)
+        n = u.shape[0]
+        shape = (n, self.n_dim) if layout == ROW_MAJOR else (self.n_keys, n)
+        out = torch.empty(shape, dtype=torch.float64, device=u.device)
+        _lib.check(self._lib.nb_prior_table_transform(
+            self._h, _ptr(u), n, layout, _ptr(out), _stream()))
+        return out
+
+
+
 
 def gmm_fit(x, n_init=10, seed=0, tol=1e-3, reg_covar=1e-6, max_iter=100,
             init_labels=None):

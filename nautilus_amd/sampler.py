@@ -113,10 +113,17 @@ class Sampler:
         self._prior_is_identity = (prior is unit_prior or
                                    getattr(prior, 'identity', False) is True)
         if self._device_likelihood and not getattr(prior, 'device', False):
+            why = ''
+            if hasattr(prior, '_device_handle'):
+                from .prior import DEVICE_FAMILIES
+                why = '; %s -- a Prior is transformed on the device if ' \
+                    'every free parameter is a frozen scipy distribution ' \
+                    'of the families %s' % (prior._cached()['obstacle'],
+                                            DEVICE_FAMILIES)
             raise ValueError(
                 'a device likelihood needs a prior transform that works on '
                 'cuda tensors (mark it with `.device = True`, e.g. '
-                'nautilus_amd.unit_prior)')
+                'nautilus_amd.unit_prior)' + why)
         if callable(prior):
             self.prior = partial(prior, *prior_args, **prior_kwargs)
             if n_dim is None:
