@@ -407,8 +407,8 @@ int nb_prior_table_transform(const nb_prior_table* table, const double* u_dev,
                              void* stream);
 
 /* Device likelihoods of the benchmark problems (the user-side callable of
- * sampler.py:863-873 for the BASELINE configurations C3 and C5; Gaussians go
- * through nb_neural_score): out_dev[i] = log L of row i of u_dev (unit-cube
+ * sampler.py:863-873 for the BASELINE configurations C3 and C5; single Gaussians
+ * go through nb_neural_score, mixtures through nb_mixture_loglike below): out_dev[i] = log L of row i of u_dev (unit-cube
  * points, n x n_dim).
  *   Rosenbrock: x = lo + (hi - lo) u,
  *               log L = -sum_i [a (x_{i+1} - x_i^2)^2 + (1 - x_i)^2]
@@ -420,6 +420,30 @@ int nb_loglike_rosenbrock(const double* u_dev, int64_t n, int32_t n_dim,
 int nb_loglike_funnel(const double* u_dev, int64_t n, int32_t n_dim, double mu,
                       double sigma0, double k, double c, double* out_dev,
                       void* stream);
+
+/* Weighted, full-covariance Gaussian mixture (the user-side callable of
+ * sampler.py:863-873 for multi-modal problems), one launch that reads every
+ * point once:
+ *   log L(x) = logsumexp_k [ log_coef_k - 1/2 |L_k^-1 (x - mu_k)|^2 ],
+ *   Sigma_k = L_k L_k^T.
+ * means [K*n_dim]; chol_inv [K*n_dim*n_dim] row-major, lower triangular L_k^-1
+ * (exact zeros above the diagonal); log_coef [K] = log w_k - D/2 log 2pi -
+ * sum log diag L_k.  All three are host arrays, read here; the packed
+ * components live in HBM.  NB_ERR_ARG: n_dim outside 1..128, n_components
+ * outside 1..NB_MIXTURE_MAX_COMPONENTS, a non-finite input, a nonzero above
+ * or a non-positive entry on the diagonal of a chol_inv.
+ * nb_mixture_loglike only launches, on the caller's stream (one handle serves
+ * any number of streams): out_dev[i] = log L of row i of x_dev (n x n_dim);
+ * label_dev may be NULL, else label_dev[i] = the first k whose term is the
+ * largest (numpy.argmax).  n = 0 returns NB_OK without a launch.             */
+typedef struct nb_mixture nb_mixture;
+#define NB_MIXTURE_MAX_COMPONENTS 4096
+int nb_mixture_create(int32_t n_dim, int32_t n_components, const double* means,
+                      const double* chol_inv, const double* log_coef,
+                      nb_mixture** out);
+int nb_mixture_loglike(const nb_mixture* mix, const double* x_dev, int64_t n,
+                       double* out_dev, int32_t* label_dev, void* stream);
+int nb_mixture_destroy(nb_mixture* mix);
 
 
 /* Two-stage evaluation of bounds with several outer members, several neural

@@ -153,6 +153,12 @@ _SIGNATURES = {
     'nb_loglike_funnel': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32,
                                     C.c_double, C.c_double, C.c_double,
                                     C.c_double, C.c_void_p, C.c_void_p]),
+    'nb_mixture_create': (C.c_int, [C.c_int32, C.c_int32, c_double_p,
+                                    c_double_p, c_double_p,
+                                    C.POINTER(C.c_void_p)]),
+    'nb_mixture_loglike': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    'nb_mixture_destroy': (C.c_int, [C.c_void_p]),
     'nb_live_append': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_int32,
                                  C.c_void_p, C.c_void_p]),

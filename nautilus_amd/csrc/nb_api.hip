@@ -1285,6 +1285,102 @@ int nb_loglike_funnel(const double* u, int64_t n, int32_t n_dim, double mu,
                           as_stream(stream));
 }
 
+// Components of a mixture packed for nb_mixture.hip: K records of
+// nb_mixture_record(dt) doubles, uploaded once.
+struct nb_mixture {
+  double* dev = nullptr;
+  int n_dim = 0, n_comp = 0;
+};
+
+int nb_mixture_create(int32_t n_dim, int32_t n_components, const double* means,
+                      const double* chol_inv, const double* log_coef,
+                      nb_mixture** out) {
+  if (out == nullptr || means == nullptr || chol_inv == nullptr ||
+      log_coef == nullptr || n_dim < 1 || n_dim > 16 * NB_MAX_DT ||
+      n_components < 1 || n_components > NB_MIXTURE_MAX_COMPONENTS) {
+    nb_set_error("bad mixture arguments (n_dim 1..%d, 1..%d components)",
+                 16 * NB_MAX_DT, NB_MIXTURE_MAX_COMPONENTS);
+    return NB_ERR_ARG;
+  }
+  *out = nullptr;
+  const int dt = (n_dim + 15) / 16;
+  const size_t d = (size_t)n_dim, cs = (size_t)nb_mixture_record(dt);
+  const size_t nt = (size_t)dt * (dt + 1) / 2;
+  std::vector<double> host(cs * (size_t)n_components, 0.0);
+  for (int c = 0; c < n_components; ++c) {
+    const double* li = chol_inv + (size_t)c * d * d;
+    const double* mu = means + (size_t)c * d;
+    if (!std::isfinite(log_coef[c])) {
+      nb_set_error("component %d: log_coef is not finite", c);
+      return NB_ERR_ARG;
+    }
+    for (int h = 0; h < n_dim; ++h) {
+      if (!std::isfinite(mu[h])) {
+        nb_set_error("component %d: mean %d is not finite", c, h);
+        return NB_ERR_ARG;
+      }
+      for (int k = 0; k < n_dim; ++k) {
+        const double v = li[h * d + k];
+        if (!std::isfinite(v) || (k > h && v != 0.0) || (k == h && !(v > 0.0))) {
+          nb_set_error("component %d: chol_inv must be finite and lower "
+                       "triangular with a positive diagonal (entry %d, %d)",
+                       c, h, k);
+          return NB_ERR_ARG;
+        }
+      }
+    }
+    // lower-triangular tiles with the K permutation of nb_stream.hip (slot
+    // 4kt+s of lane group lg <-> feature 16kt + 8(s>>1) + 2lg + (s&1))
+    double* rec = &host[cs * (size_t)c];
+    for (int ht = 0; ht < dt; ++ht)
+      for (int kt = 0; kt <= ht; ++kt)
+        for (int s4 = 0; s4 < 4; ++s4)
+          for (int lg = 0; lg < 4; ++lg)
+            for (int l = 0; l < 16; ++l) {
+              const int k = 16 * kt + 8 * (s4 >> 1) + 2 * lg + (s4 & 1);
+              const int h = 16 * ht + l;
+              if (h < n_dim && k <= h)
+                rec[((size_t)(ht * (ht + 1)) / 2 + kt) * NB_TILE + s4 * 64 +
+                    lg * 16 + l] = li[h * d + k];
+            }
+    double* tail = rec + nt * NB_TILE;
+    for (int h = 0; h < n_dim; ++h) tail[h] = mu[h];
+    tail[16 * dt] = log_coef[c];
+  }
+  nb_mixture* m = new nb_mixture;
+  m->n_dim = n_dim;
+  m->n_comp = n_components;
+  const size_t bytes = host.size() * sizeof(double);
+  hipError_t e = hipMalloc((void**)&m->dev, bytes);
+  if (e == hipSuccess)
+    e = hipMemcpy(m->dev, host.data(), bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    nb_set_error("mixture upload failed: %s", hipGetErrorString(e));
+    if (m->dev != nullptr) (void)hipFree(m->dev);
+    delete m;
+    return NB_ERR_HIP;
+  }
+  *out = m;
+  return NB_OK;
+}
+
+int nb_mixture_destroy(nb_mixture* mix) {
+  if (mix == nullptr) return NB_OK;
+  (void)hipFree(mix->dev);
+  delete mix;
+  return NB_OK;
+}
+
+int nb_mixture_loglike(const nb_mixture* mix, const double* x, int64_t n,
+                       double* out, int32_t* label, void* stream) {
+  if (mix == nullptr || n < 0 || (n > 0 && (x == nullptr || out == nullptr))) {
+    nb_set_error("bad mixture likelihood arguments");
+    return NB_ERR_ARG;
+  }
+  return nb_launch_mixture(mix->dev, mix->n_dim, mix->n_comp, x, n, out, label,
+                           as_stream(stream));
+}
+
 int nb_live_append(const double* log_l, int64_t n, const double* thr,
                    double* pool, int32_t* pool_n, int32_t capacity,
                    int32_t* overflow, void* stream) {

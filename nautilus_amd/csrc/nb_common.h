@@ -97,6 +97,19 @@ __host__ __device__ inline int nb_net_tiles(int kt1) {
   return kt1 * NB_HT1 + NB_HT1 * NB_HT2 + NB_HT2 * NB_HT3 + NB_HT3 * 1;
 }
 
+// One component of a Gaussian mixture (nb_mixture.hip) is a record of
+// DT(DT+1)/2 tiles of L^-1, then a tail: mu[16 DT], a_k, padding up to a
+// multiple of the 1 KB a wavefront copies per global_load_lds instruction
+__host__ __device__ constexpr int nb_mixture_tail(int dt) {
+  return (16 * dt + 1 + 127) / 128 * 128;
+}
+__host__ __device__ constexpr int nb_mixture_record(int dt) {
+  return dt * (dt + 1) / 2 * NB_TILE + nb_mixture_tail(dt);
+}
+int nb_launch_mixture(const double* blob, int n_dim, int n_comp,
+                      const double* x, long long n, double* out, int* label,
+                      hipStream_t stream);
+
 // One (bound, neural bound) group of a two-stage query (nb_cand.hip ->
 // nb_eval_fast.hip, BATCH): built on the host when a bound / a bound list is
 // created, read by the second stage per 128-point pass.

@@ -582,6 +582,48 @@ class PriorTable:
         return out
 
 
+class MixtureTable:
+    """Device-resident components of a Gaussian mixture
+    (``nb_mixture_create``): means (K, D), the lower-triangular inverse
+    Cholesky factors ``chol_inv`` (K, D, D) and ``log_coef`` (K,) = log w_k -
+    D/2 log 2 pi - sum log diag L_k.  Packed and uploaded once; every
+    ``loglike`` is one launch on the current stream."""
+
+    def __init__(self, means, chol_inv, log_coef):
+        self._lib = lib = _lib.load()
+        means = _f64(means)
+        chol_inv = _f64(chol_inv)
+        log_coef = _f64(log_coef)
+        if means.ndim != 2 or chol_inv.shape != means.shape + means.shape[1:] \
+                or log_coef.shape != means.shape[:1]:
+            raise ValueError('mixture arrays differ in shape')
+        self.n_components, self.n_dim = means.shape
+        h = C.c_void_p()
+        _lib.check(lib.nb_mixture_create(
+            self.n_dim, self.n_components, _dp(means), _dp(chol_inv),
+            _dp(log_coef), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, '_h', None)
+        if h:
+            self._lib.nb_mixture_destroy(h)
+            self._h = None
+
+    def loglike(self, x, labels=False):
+        """log L of the rows of ``x`` as a cuda tensor; with ``labels`` also
+        the int32 index of the largest term of every row."""
+        x = as_device_points(x, self.n_dim)
+        n = x.shape[0]
+        out = torch.empty(n, dtype=torch.float64, device=x.device)
+        lab = torch.empty(n, dtype=torch.int32, device=x.device) \
+            if labels else None
+        _lib.check(self._lib.nb_mixture_loglike(
+            self._h, _ptr(x), n, _ptr(out),
+            _ptr(lab) if labels else None, _stream()))
+        return (out, lab) if labels else out
+
+
 
 
 def gmm_fit(x, n_init=10, seed=0, tol=1e-3, reg_covar=1e-6, max_iter=100,

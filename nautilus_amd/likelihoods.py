@@ -68,27 +68,130 @@ class GaussianLikelihood:
 
 
 class GaussianMixtureLikelihood:
-    """Equal-weight mixture of isotropic Gaussians (BASELINE config 4)."""
+    """Mixture of Gaussians  log sum_k w_k N(x; mu_k, Sigma_k).
+
+    ``GaussianMixtureLikelihood(means, sigma)`` is the equal-weight isotropic
+    mixture of BASELINE config 4, a composition of ``GaussianLikelihood``
+    parts.  Any of ``covs`` ((D, D) shared or (K, D, D)), ``weights`` (K
+    positive numbers, normalised by their sum) or ``labels=True`` selects the
+    fused kernel ``nb_mixture_loglike`` instead: one launch that reads every
+    point once, for unequal weights and correlated components.  With
+    ``labels=True`` a call returns ``(log_l, label)``, ``label`` being the
+    int32 index of the largest term (the component a point belongs to);
+    ``Sampler`` carries it through as a blob."""
 
     device = True
 
-    def __init__(self, means, sigma):
+    def __init__(self, means, sigma=None, *, covs=None, weights=None,
+                 labels=False):
         self.means = np.atleast_2d(np.asarray(means, float))
-        self.sigma = float(sigma)
-        d = self.means.shape[1]
-        self.parts = [GaussianLikelihood(m, np.eye(d) * sigma**2)
-                      for m in self.means]
+        if (sigma is None) == (covs is None):
+            raise ValueError('exactly one of sigma and covs must be given')
+        self.sigma = None if sigma is None else float(sigma)
+        k, d = self.means.shape
+        self.n_components, self.n_dim = k, d
+        self.labels = bool(labels)
+        self.fused = covs is not None or weights is not None or self.labels
+        if not self.fused:
+            self.parts = [GaussianLikelihood(m, np.eye(d) * sigma**2)
+                          for m in self.means]
+            self.covs = np.broadcast_to(np.eye(d) * self.sigma**2,
+                                        (k, d, d)).copy()
+            self.weights = np.full(k, 1.0 / k)
+            return
+        self.parts = None
+        if not np.all(np.isfinite(self.means)):
+            raise ValueError('means must be finite')
+        if covs is None:
+            if not (np.isfinite(self.sigma) and self.sigma > 0):
+                raise ValueError('sigma must be positive and finite')
+            covs = np.eye(d) * self.sigma**2
+        covs = np.asarray(covs, float)
+        if covs.shape == (d, d):
+            covs = np.broadcast_to(covs, (k, d, d))
+        if covs.shape != (k, d, d):
+            raise ValueError('covs must have shape (%d, %d) or (%d, %d, %d), '
+                             'not %s' % (d, d, k, d, d, covs.shape))
+        self.covs = covs.copy()
+        if weights is None:
+            weights = np.full(k, 1.0)
+        weights = np.asarray(weights, float)
+        if weights.shape != (k,) or not np.all(np.isfinite(weights)) or \
+                not np.all(weights > 0):
+            raise ValueError('weights must be %d positive finite numbers' % k)
+        self.weights = weights / np.sum(weights)
+        self._chol = np.empty((k, d, d))
+        for i in range(k):
+            try:
+                if not np.all(np.isfinite(self.covs[i])):
+                    raise np.linalg.LinAlgError('not finite')
+                self._chol[i] = np.linalg.cholesky(self.covs[i])
+            except np.linalg.LinAlgError:
+                raise ValueError('the covariance of component %d is not '
+                                 'positive definite' % i) from None
+        self._log_coef = (np.log(self.weights) - 0.5 * d * np.log(2 * np.pi) -
+                          np.sum(np.log(np.diagonal(self._chol, axis1=1,
+                                                    axis2=2)), axis=1))
+        self._tables = {}
+
+    def _table(self):
+        """The device handle of the current device, built on first use."""
+        dev = torch.cuda.current_device()
+        if dev not in self._tables:
+            from scipy.linalg import solve_triangular
+            eye = np.eye(self.n_dim)
+            chol_inv = np.stack([
+                np.tril(solve_triangular(c, eye, lower=True))
+                for c in self._chol])
+            self._tables[dev] = device.MixtureTable(self.means, chol_inv,
+                                                    self._log_coef)
+        return self._tables[dev]
 
     def __call__(self, x):
-        xs = device.as_device_points(x)
-        stack = torch.stack([p(xs) for p in self.parts])
-        out = torch.logsumexp(stack, dim=0) - np.log(len(self.parts))
-        return out if isinstance(x, torch.Tensor) else out.cpu().numpy()
+        if not self.fused:
+            xs = device.as_device_points(x)
+            stack = torch.stack([p(xs) for p in self.parts])
+            out = torch.logsumexp(stack, dim=0) - np.log(len(self.parts))
+            return out if isinstance(x, torch.Tensor) else out.cpu().numpy()
+        res = self._table().loglike(x, labels=self.labels)
+        if isinstance(x, torch.Tensor):
+            return res
+        if self.labels:
+            return res[0].cpu().numpy(), res[1].cpu().numpy()
+        return res.cpu().numpy()
 
-    def numpy(self, x):
+    def numpy(self, x, labels=False):
+        """Pure-numpy evaluation (CPU baseline / oracle runs / tests); with
+        ``labels`` also the index of the largest term."""
         from scipy.special import logsumexp
-        return logsumexp([p.numpy(x) for p in self.parts], axis=0) - \
-            np.log(len(self.parts))
+        if not self.fused:
+            parts = [p.numpy(x) for p in self.parts]
+            out = logsumexp(parts, axis=0) - np.log(len(self.parts))
+            if labels:
+                return out, np.argmax(parts, axis=0).astype(np.int32)
+            return out
+        terms = self._terms(x)
+        out = logsumexp(terms, axis=0)
+        if labels:
+            return out, np.argmax(terms, axis=0).astype(np.int32)
+        return out
+
+    def _terms(self, x):
+        """(K, n) array of log w_k N(x_i; mu_k, Sigma_k)."""
+        from scipy.linalg import solve_triangular
+        x = np.atleast_2d(np.asarray(x, float))
+        terms = np.empty((self.n_components, x.shape[0]))
+        for i in range(self.n_components):
+            y = solve_triangular(self._chol[i], (x - self.means[i]).T,
+                                 lower=True)
+            terms[i] = self._log_coef[i] - 0.5 * np.sum(y**2, axis=0)
+        return terms
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        if '_tables' in state:
+            state['_tables'] = {}
+        return state
 
 
 class RosenbrockLikelihood:
