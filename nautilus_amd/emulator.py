@@ -27,6 +27,8 @@ EPOCH_CHUNK = 16     # epochs per kernel launch (host prepares the next chunk
 CHUNK_BYTES = 32 << 20   # ... fewer where a chunk's orders would exceed this
 MAX_BATCH = 4096     # largest minibatch of the device trainer
                      # (NB_TRAIN_MAX_BATCH, include/nautilus_hip.h)
+MAX_ITER = 10000     # most epochs of a fit (the length of the loss curve the
+                     # trainer allocates; nb_trainer_set_hparams)
 
 
 class Network:
@@ -254,7 +256,7 @@ def _hparams_from_kwargs(kwargs):
         elif key == 'batch_size':
             hp['batch'] = _check_batch_size(val)
         elif key in known:
-            hp[known[key]] = val
+            hp[known[key]] = _check_hparam(key, val)
         elif key == 'hidden_layer_sizes':
             hp['hidden'] = check_hidden(val)
         elif key in fixed:
@@ -267,6 +269,41 @@ def _hparams_from_kwargs(kwargs):
             raise ValueError(
                 'MLPRegressor option %r is not supported on the device' % key)
     return hp
+
+
+def _is_real(val):
+    return (isinstance(val, numbers.Real)
+            and not isinstance(val, (bool, np.bool_)))
+
+
+def _is_int(val):
+    return (isinstance(val, numbers.Integral)
+            and not isinstance(val, (bool, np.bool_)))
+
+
+def _check_hparam(key, val):
+    """scikit-learn's ranges for Adam's constants and the stopping rule
+    (``MLPRegressor._parameter_constraints``), with the device trainer's
+    limits on top: at most MAX_ITER epochs, and ``n_iter_no_change`` an
+    integer (scikit-learn also takes ``np.inf``).  The comparisons are written
+    so that NaN fails them."""
+    if key in ('learning_rate_init', 'epsilon'):
+        ok, want = _is_real(val) and 0 < val < np.inf, 'a real number > 0'
+    elif key in ('beta_1', 'beta_2'):
+        ok, want = _is_real(val) and 0 <= val < 1, 'a real number in [0, 1)'
+    elif key == 'tol':
+        ok, want = _is_real(val) and 0 <= val < np.inf, 'a real number >= 0'
+    elif key == 'n_iter_no_change':
+        ok = _is_int(val) and 1 <= val <= np.iinfo(np.int32).max
+        want = 'an integer >= 1'
+    else:
+        assert key == 'max_iter'
+        ok = _is_int(val) and 1 <= val <= MAX_ITER
+        want = ('an integer from 1 to %d (the device trainer holds fits of '
+                'at most %d epochs)' % (MAX_ITER, MAX_ITER))
+    if not ok:
+        raise ValueError('%s must be %s; got %r' % (key, want, val))
+    return int(val) if key in ('n_iter_no_change', 'max_iter') else float(val)
 
 
 def _check_batch_size(val):

@@ -120,7 +120,8 @@ class Network:
 @threadpool_limits.wrap(limits=1)                       # neural.py:10
 def fit_network(x, y, random_state, max_iter=10000, n_iter_no_change=10,
                 tol=0.0, batch_size=200, lr=1e-2, permutations=None,
-                init=None, hidden=HIDDEN):
+                init=None, hidden=HIDDEN, beta_1=0.9, beta_2=0.999,
+                epsilon=1e-8):
     """``MLPRegressor(random_state=i, ...).fit(x, y)`` restated
     (sklearn/_multilayer_perceptron.py:620-760).
 
@@ -129,6 +130,8 @@ def fit_network(x, y, random_state, max_iter=10000, n_iter_no_change=10,
         oracle with the same minibatch order).
     init : optional (coefs, intercepts) replacing the Glorot draw.
     hidden : ``hidden_layer_sizes`` (neural.py:79-83 passes it through).
+    beta_1, beta_2, epsilon : Adam's constants (MLPRegressor options of the
+        same names).
     """
     n, d = x.shape
     y2 = y.reshape(-1, 1)
@@ -136,7 +139,7 @@ def fit_network(x, y, random_state, max_iter=10000, n_iter_no_change=10,
     if init is not None:
         coefs = [np.array(c, float) for c in init[0]]
         intercepts = [np.array(c, float) for c in init[1]]
-    opt = Adam(coefs + intercepts, lr=lr)
+    opt = Adam(coefs + intercepts, lr=lr, b1=beta_1, b2=beta_2, eps=epsilon)
     bs = min(batch_size, n)
     sample_idx = np.arange(n, dtype=int)
     best, stale = np.inf, 0
@@ -177,7 +180,7 @@ class Emulator:
         self.mean = np.mean(x, axis=0)
         self.scale = np.std(x, axis=0)
         kw = dict(max_iter=10000, n_iter_no_change=10, tol=0.0,
-                  lr=1e-2)
+                  lr=1e-2, beta_1=0.9, beta_2=0.999, epsilon=1e-8)
         for key, val in neural_network_kwargs.items():
             if key == 'learning_rate_init':
                 kw['lr'] = val
