@@ -445,6 +445,32 @@ int nb_mixture_loglike(const nb_mixture* mix, const double* x_dev, int64_t n,
                        double* out_dev, int32_t* label_dev, void* stream);
 int nb_mixture_destroy(nb_mixture* mix);
 
+/* Gaussian likelihood of a data vector (the user-side callable of
+ * sampler.py:863-873 for a model prediction m(theta) of P data points compared
+ * with measurements d under a covariance C = L L^T), one launch that reads
+ * every model row once and never stores the n x P product:
+ *   out_dev[i] = log_norm - 1/2 |W (m_i - d)|^2,   W = L^-1.
+ * data [P]; chol_inv [P*P] row-major, lower triangular L^-1 (exact zeros above
+ * the diagonal), or NULL; inv_sigma [P] = 1 / sigma for a diagonal C, or NULL:
+ * exactly one of the two.  All are host arrays, read here; W is packed as
+ * lower-triangle operand tiles and uploaded once.  NB_ERR_ARG: n_data outside
+ * 1..NB_CHI2_MAX_DATA, both or neither of chol_inv and inv_sigma, a non-finite
+ * input, a nonzero above or a non-positive entry on the diagonal of chol_inv,
+ * a non-positive inv_sigma.
+ * nb_chi2_loglike only launches, on the caller's stream (one handle serves any
+ * number of streams): row i of the model is the n_data doubles at model_dev +
+ * i * ld (NB_ERR_ARG for ld < n_data).  A non-finite entry of a row makes that
+ * row's result NaN and changes no other row.  The bits of a row depend on
+ * neither n, its position in the batch, ld nor the stream.  n = 0 returns
+ * NB_OK without a launch.                                                   */
+typedef struct nb_chi2 nb_chi2;
+#define NB_CHI2_MAX_DATA 4096
+int nb_chi2_create(int32_t n_data, const double* data, const double* chol_inv,
+                   const double* inv_sigma, double log_norm, nb_chi2** out);
+int nb_chi2_loglike(const nb_chi2* h, const double* model_dev, int64_t ld,
+                    int64_t n, double* out_dev, void* stream);
+int nb_chi2_destroy(nb_chi2* h);
+
 
 /* Two-stage evaluation of bounds with several outer members, several neural
  * bounds, or of lists of bounds (bounds/union.py:285-289, 316-319;

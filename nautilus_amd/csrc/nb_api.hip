@@ -4,6 +4,7 @@
 #include "nb_common.h"
 #include "../../include/nautilus_hip.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -1379,6 +1380,123 @@ int nb_mixture_loglike(const nb_mixture* mix, const double* x, int64_t n,
   }
   return nb_launch_mixture(mix->dev, mix->n_dim, mix->n_comp, x, n, out, label,
                            as_stream(stream));
+}
+
+// Data vector and W = L^-1 (or 1 / sigma) packed for nb_chi2.hip
+// (nb_common.h, nb_chi2_w_offset), uploaded once.
+struct nb_chi2 {
+  double* dev = nullptr;
+  int n_data = 0;
+  bool diag = false;
+  double log_norm = 0.0;
+};
+
+int nb_chi2_create(int32_t n_data, const double* data, const double* chol_inv,
+                   const double* inv_sigma, double log_norm, nb_chi2** out) {
+  if (out == nullptr || data == nullptr || n_data < 1 ||
+      n_data > NB_CHI2_MAX_DATA ||
+      (chol_inv == nullptr) == (inv_sigma == nullptr) ||
+      !std::isfinite(log_norm)) {
+    nb_set_error("bad data likelihood arguments (n_data 1..%d, exactly one "
+                 "of chol_inv and inv_sigma, a finite log_norm)",
+                 NB_CHI2_MAX_DATA);
+    return NB_ERR_ARG;
+  }
+  *out = nullptr;
+  const size_t p = (size_t)n_data;
+  for (size_t k = 0; k < p; ++k)
+    if (!std::isfinite(data[k])) {
+      nb_set_error("data %zu is not finite", k);
+      return NB_ERR_ARG;
+    }
+  std::vector<double> host;
+  if (inv_sigma != nullptr) {
+    host.assign(2 * p, 0.0);
+    for (size_t k = 0; k < p; ++k) {
+      if (!std::isfinite(inv_sigma[k]) || !(inv_sigma[k] > 0.0)) {
+        nb_set_error("inv_sigma %zu must be positive and finite", k);
+        return NB_ERR_ARG;
+      }
+      host[k] = data[k];
+      host[p + k] = inv_sigma[k];
+    }
+  } else {
+    for (size_t h = 0; h < p; ++h)
+      for (size_t k = 0; k < p; ++k) {
+        const double v = chol_inv[h * p + k];
+        if (!std::isfinite(v) || (k > h && v != 0.0) || (k == h && !(v > 0.0))) {
+          nb_set_error("chol_inv must be finite and lower triangular with a "
+                       "positive diagonal (entry %zu, %zu)", h, k);
+          return NB_ERR_ARG;
+        }
+      }
+    const int dt = (n_data + 15) / 16;
+    const int n_panels = (dt + NB_CHI2_PANEL - 1) / NB_CHI2_PANEL;
+    size_t tiles = 0;
+    for (int pn = 0; pn < n_panels; ++pn) {
+      const int nrt = std::min(NB_CHI2_PANEL, dt - NB_CHI2_PANEL * pn);
+      tiles += (size_t)nrt * (size_t)(NB_CHI2_PANEL * pn + nrt);
+    }
+    host.assign((size_t)nb_chi2_w_offset(dt) + tiles * NB_TILE, 0.0);
+    for (size_t k = 0; k < p; ++k) host[k] = data[k];
+    // operand tiles: lane group lg of k-step s holds column 4 lg + s of the
+    // k-tile (what a staging thread of the kernel reads as 32 contiguous
+    // bytes of a model row)
+    double* tile = host.data() + nb_chi2_w_offset(dt);
+    for (int pn = 0; pn < n_panels; ++pn) {
+      const int nrt = std::min(NB_CHI2_PANEL, dt - NB_CHI2_PANEL * pn);
+      for (int kt = 0; kt < NB_CHI2_PANEL * pn + nrt; ++kt)
+        for (int ti = 0; ti < nrt; ++ti, tile += NB_TILE) {
+          const int rt = NB_CHI2_PANEL * pn + ti;
+          if (kt > rt) continue;                 // above the diagonal: zeros
+          for (int s = 0; s < 4; ++s)
+            for (int lg = 0; lg < 4; ++lg)
+              for (int l = 0; l < 16; ++l) {
+                const size_t h = 16 * (size_t)rt + l;
+                const size_t k = 16 * (size_t)kt + 4 * lg + s;
+                if (h < p && k <= h)
+                  tile[s * 64 + lg * 16 + l] = chol_inv[h * p + k];
+              }
+        }
+    }
+  }
+  nb_chi2* c = new nb_chi2;
+  c->n_data = n_data;
+  c->diag = inv_sigma != nullptr;
+  c->log_norm = log_norm;
+  const size_t bytes = host.size() * sizeof(double);
+  hipError_t e = hipMalloc((void**)&c->dev, bytes);
+  if (e == hipSuccess)
+    e = hipMemcpy(c->dev, host.data(), bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    nb_set_error("data likelihood upload failed: %s", hipGetErrorString(e));
+    if (c->dev != nullptr) (void)hipFree(c->dev);
+    delete c;
+    return NB_ERR_HIP;
+  }
+  *out = c;
+  return NB_OK;
+}
+
+int nb_chi2_destroy(nb_chi2* h) {
+  if (h == nullptr) return NB_OK;
+  (void)hipFree(h->dev);
+  delete h;
+  return NB_OK;
+}
+
+int nb_chi2_loglike(const nb_chi2* h, const double* model, int64_t ld,
+                    int64_t n, double* out, void* stream) {
+  if (h == nullptr || n < 0 || ld < h->n_data ||
+      (n > 0 && (model == nullptr || out == nullptr))) {
+    nb_set_error("bad data likelihood arguments (ld >= n_data)");
+    return NB_ERR_ARG;
+  }
+  if (h->diag)
+    return nb_launch_chi2_diag(h->dev, h->n_data, model, ld, n, h->log_norm,
+                               out, as_stream(stream));
+  return nb_launch_chi2(h->dev, h->n_data, model, ld, n, h->log_norm, out,
+                        as_stream(stream));
 }
 
 int nb_live_append(const double* log_l, int64_t n, const double* thr,

@@ -110,6 +110,23 @@ int nb_launch_mixture(const double* blob, int n_dim, int n_comp,
                       const double* x, long long n, double* out, int* label,
                       hipStream_t stream);
 
+// Gaussian likelihood of a data vector (nb_chi2.hip).  Full covariance: the
+// blob is d zero padded to 16 DT doubles (rounded up to the 1 KB of a
+// global_load_lds piece), then W = L^-1 as 16x16 operand tiles in the order
+// the kernel walks them: panels of NB_CHI2_PANEL row tiles; per panel the
+// k-tiles 0 .. its last row tile; per k-tile the panel's row tiles.  Diagonal
+// covariance: d [P], then 1 / sigma [P].
+#define NB_CHI2_PANEL 16
+__host__ __device__ constexpr int nb_chi2_w_offset(int dt) {
+  return (16 * dt + 127) / 128 * 128;
+}
+int nb_launch_chi2(const double* blob, int n_data, const double* model,
+                   long long ld, long long n, double log_norm, double* out,
+                   hipStream_t stream);
+int nb_launch_chi2_diag(const double* blob, int n_data, const double* model,
+                        long long ld, long long n, double log_norm,
+                        double* out, hipStream_t stream);
+
 // One (bound, neural bound) group of a two-stage query (nb_cand.hip ->
 // nb_eval_fast.hip, BATCH): built on the host when a bound / a bound list is
 // created, read by the second stage per 128-point pass.

@@ -624,6 +624,53 @@ class MixtureTable:
         return (out, lab) if labels else out
 
 
+class Chi2Table:
+    """Device-resident data vector of a Gaussian likelihood
+    (``nb_chi2_create``): ``data`` (P,) and either the lower-triangular
+    inverse Cholesky factor ``chol_inv`` (P, P) of the covariance or
+    ``inv_sigma`` (P,) = 1 / sigma of a diagonal one.  Packed and uploaded
+    once; every ``loglike`` is one launch on the current stream."""
+
+    def __init__(self, data, chol_inv=None, inv_sigma=None, log_norm=0.0):
+        self._lib = lib = _lib.load()
+        data = _f64(data)
+        if data.ndim != 1:
+            raise ValueError('data must be one-dimensional')
+        self.n_data = p = len(data)
+        if chol_inv is not None:
+            chol_inv = _f64(chol_inv)
+            if chol_inv.shape != (p, p):
+                raise ValueError('chol_inv must have shape (%d, %d)' % (p, p))
+        if inv_sigma is not None:
+            inv_sigma = _f64(inv_sigma)
+            if inv_sigma.shape != (p,):
+                raise ValueError('inv_sigma must have shape (%d,)' % p)
+        h = C.c_void_p()
+        _lib.check(lib.nb_chi2_create(
+            p, _dp(data), None if chol_inv is None else _dp(chol_inv),
+            None if inv_sigma is None else _dp(inv_sigma), float(log_norm),
+            C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, '_h', None)
+        if h:
+            self._lib.nb_chi2_destroy(h)
+            self._h = None
+
+    def loglike(self, model, ld=None):
+        """log L of the rows of the cuda float64 tensor ``model`` (n, P),
+        read in place: its rows may be strided (``stride(1) == 1``,
+        ``stride(0) >= P``).  ``ld`` overrides the row stride (in doubles)
+        the tensor reports."""
+        n = model.shape[0]
+        if ld is None:
+            ld = model.stride(0) if n > 1 else self.n_data
+        out = torch.empty(n, dtype=torch.float64, device=model.device)
+        _lib.check(self._lib.nb_chi2_loglike(
+            self._h, _ptr(model), ld, n, _ptr(out), _stream()))
+        return out
+
 
 
 def gmm_fit(x, n_init=10, seed=0, tol=1e-3, reg_covar=1e-6, max_iter=100,

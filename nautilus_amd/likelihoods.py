@@ -194,6 +194,157 @@ class GaussianMixtureLikelihood:
         return state
 
 
+N_DATA_MAX = 4096                  # NB_CHI2_MAX_DATA of include/nautilus_hip.h
+
+
+class GaussianDataLikelihood:
+    """Gaussian likelihood of a data vector:  log L(theta) = log_norm -
+    1/2 (m(theta) - d)^T C^-1 (m(theta) - d).
+
+    ``model`` takes the (n, n_dim) batch of points as a torch tensor and
+    returns the (n, P) float64 predictions on the same device; ``data`` holds
+    the P measurements; exactly one of ``cov`` ((P, P), symmetric positive
+    definite) and ``sigma`` (P positive numbers, a diagonal covariance) is
+    given.  P is at most 4096.  ``log_norm = -1/2 (P log 2 pi + log det C)``,
+    or 0 with ``normalised=False``.
+
+    A call evaluates the model and then runs the fused kernel
+    ``nb_chi2_loglike`` -- one launch on the current stream that multiplies by
+    the triangle of W = L^-1 (C = L L^T) only and never stores the n x P
+    product.  ``from_model`` is the second half alone; it reads a cuda tensor
+    whose rows are strided (``stride(1) == 1``, ``stride(0) >= P``, such as a
+    column slice of a wider tensor) in place and copies anything else to
+    contiguous.  ``numpy`` / ``numpy_from_model`` are the pure-numpy twins.
+
+    A non-finite entry in row i of the model output makes ``out[i]`` NaN and
+    changes no bit of any other row."""
+
+    device = True
+
+    def __init__(self, model, data, *, cov=None, sigma=None, normalised=True):
+        if not callable(model):
+            raise ValueError('model must be callable')
+        self.model = model
+        data = np.asarray(data, float)
+        if data.ndim != 1 or len(data) < 1:
+            raise ValueError('data must be a vector of at least one number')
+        if len(data) > N_DATA_MAX:
+            raise ValueError('at most %d data points are supported, not %d' %
+                             (N_DATA_MAX, len(data)))
+        if not np.all(np.isfinite(data)):
+            raise ValueError('data must be finite')
+        if (cov is None) == (sigma is None):
+            raise ValueError('exactly one of cov and sigma must be given')
+        self.data = data.copy()
+        self.n_data = p = len(data)
+        self.cov = self.sigma = self._chol = None
+        if sigma is not None:
+            sigma = np.asarray(sigma, float)
+            if sigma.shape != (p,) or not np.all(np.isfinite(sigma)) or \
+                    not np.all(sigma > 0):
+                raise ValueError('sigma must be %d positive finite numbers'
+                                 % p)
+            self.sigma = sigma.copy()
+            log_det = 2.0 * np.sum(np.log(sigma))
+        else:
+            cov = np.asarray(cov, float)
+            if cov.shape != (p, p):
+                raise ValueError('cov must have shape (%d, %d), not %s' %
+                                 (p, p, cov.shape))
+            try:
+                if not np.all(np.isfinite(cov)) or \
+                        not np.allclose(cov, cov.T, rtol=1e-10, atol=0.0):
+                    raise np.linalg.LinAlgError('not symmetric and finite')
+                self._chol = np.linalg.cholesky(cov)
+            except np.linalg.LinAlgError:
+                raise ValueError('cov is not positive definite (symmetric, '
+                                 'finite, every eigenvalue positive)') \
+                    from None
+            self.cov = cov.copy()
+            log_det = 2.0 * np.sum(np.log(np.diag(self._chol)))
+        self.log_norm = (-0.5 * (p * np.log(2 * np.pi) + log_det)
+                         if normalised else 0.0)
+        self._tables = {}
+
+    def _table(self):
+        """The device handle of the current device, built on first use."""
+        dev = torch.cuda.current_device()
+        if dev not in self._tables:
+            if self.sigma is not None:
+                table = device.Chi2Table(self.data, inv_sigma=1.0 / self.sigma,
+                                         log_norm=self.log_norm)
+            else:
+                from scipy.linalg import solve_triangular
+                chol_inv = np.tril(solve_triangular(
+                    self._chol, np.eye(self.n_data), lower=True))
+                table = device.Chi2Table(self.data, chol_inv=chol_inv,
+                                         log_norm=self.log_norm)
+            self._tables[dev] = table
+        return self._tables[dev]
+
+    def _check(self, m):
+        if m.ndim != 2 or m.shape[1] != self.n_data:
+            raise ValueError('the model output must have shape (n, %d), not '
+                             '%s' % (self.n_data, tuple(m.shape)))
+
+    def from_model(self, m):
+        """log L of the rows of an (n, P) float64 model output: a cuda tensor
+        in, a cuda tensor out; numpy in, numpy out."""
+        if isinstance(m, torch.Tensor):
+            if m.dtype != torch.float64:
+                raise ValueError('the model output must be float64, not %s' %
+                                 m.dtype)
+            self._check(m)
+            t = m if m.is_cuda else m.cuda()
+            p = self.n_data
+            in_place = (p == 1 or t.stride(1) == 1) and \
+                (t.shape[0] <= 1 or t.stride(0) >= p)
+            return self._table().loglike(t if in_place else t.contiguous())
+        m = np.asarray(m)
+        if m.dtype != np.float64:
+            raise ValueError('the model output must be float64, not %s' %
+                             m.dtype)
+        self._check(m)
+        t = torch.from_numpy(np.ascontiguousarray(m)).cuda()
+        return self._table().loglike(t).cpu().numpy()
+
+    def __call__(self, x):
+        if isinstance(x, torch.Tensor):
+            return self.from_model(self.model(x))
+        xs = device.as_device_points(x)
+        return self.from_model(self.model(xs)).cpu().numpy()
+
+    def numpy_from_model(self, m):
+        """Pure-numpy evaluation of an (n, P) model output (CPU baseline /
+        oracle runs / tests)."""
+        m = np.asarray(m, float)
+        self._check(m)
+        r = m - self.data
+        if self.sigma is not None:
+            y = r / self.sigma
+        else:
+            from scipy.linalg import solve_triangular
+            finite = np.where(np.isfinite(r), r, 0.0)
+            y = solve_triangular(self._chol, finite.T, lower=True,
+                                 check_finite=False).T
+        out = self.log_norm - 0.5 * np.sum(y**2, axis=1)
+        out[~np.all(np.isfinite(r), axis=1)] = np.nan
+        return out
+
+    def numpy(self, x):
+        """Pure-numpy twin of a call: the model runs on the CPU."""
+        x = np.atleast_2d(np.asarray(x, float))
+        m = self.model(torch.from_numpy(x))
+        if isinstance(m, torch.Tensor):
+            m = m.detach().cpu().numpy()
+        return self.numpy_from_model(m)
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state['_tables'] = {}
+        return state
+
+
 class RosenbrockLikelihood:
     """Rosenbrock function on x = low + (high - low) u (BASELINE config 3):
     log L = -sum_i [a (x_{i+1} - x_i^2)^2 + (1 - x_i)^2] --
