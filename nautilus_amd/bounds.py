@@ -483,9 +483,21 @@ class _RejectionSampler(_DeviceBoundBase):
         come to the host now (no wait if the launch has finished meanwhile),
         the rows move into the queue, the slot is free again."""
         pending, self._pending = self._pending, None
+        # (queue, counters and stream are ahead of what the last checkpoint
+        # says of this bound: Sampler.write_shell_update)
+        self._landed = True
         for rows, counts, n_draw, slot in pending:
             _PrefetchSlots.release(slot)
             self._collect(rows, counts.cpu().numpy(), n_draw)
+
+    def land(self):
+        """Land the refill in flight, if there is one (a checkpoint holds the
+        state of one moment: ``Sampler.write`` / ``write_shell_update``).
+        True if there was one."""
+        if self.__dict__.get('_pending') is None:
+            return False
+        self._land_pending()
+        return True
 
     def prefetch(self, n_points):
         """Launch the refill that ``sample_device(n_points)`` would need --
@@ -536,6 +548,7 @@ class _RejectionSampler(_DeviceBoundBase):
             self._land_pending()
         state = super().__getstate__()
         state.pop('_pending', None)
+        state.pop('_landed', None)
         return state
 
     @property

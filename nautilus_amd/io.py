@@ -96,6 +96,9 @@ def write_bound(bound, group):
             write_bound(bound.ellipsoid, group.create_group('ellipsoid'))
         _write_stream(bound, group)
     elif isinstance(bound, nb.Union):
+        # the queue first: looking at it lands a refill in flight, which
+        # advances the counters and has advanced the stream
+        points = bound.points
         group.attrs['type'] = 'MultiEllipsoid'
         for key in ['n_dim', 'log_v_all', 'enlarge_per_dim', 'n_points_min',
                     'n_sample', 'n_reject']:
@@ -108,7 +111,7 @@ def write_bound(bound, group):
             write_bound(member, group.create_group('bound_{}'.format(i)))
         for i, pts in enumerate(bound.points_bounds):
             group.create_dataset('points_bound_{}'.format(i), data=pts)
-        group.create_dataset('points', data=bound.points,
+        group.create_dataset('points', data=points,
                              maxshape=(None, bound.n_dim))
         group.attrs['amd_block'] = np.asarray(bound.block, dtype=bool)
         _write_stream(bound, group)
@@ -119,6 +122,9 @@ def write_bound(bound, group):
         if bound.emulator is not None:
             write_emulator(bound.emulator, group.create_group('emulator'))
     elif isinstance(bound, nb.NautilusBound):
+        # the queue first (see Union): a refill in flight also advances the
+        # counters of the envelope, which is written before 'points'
+        raw = bound.points
         group.attrs['type'] = 'NautilusBound'
         group.attrs['n_dim'] = bound.n_dim
         if bound.shift is not None:
@@ -134,7 +140,7 @@ def write_bound(bound, group):
             # the device queue itself (sampler frame): a resumed run of THIS
             # implementation continues bit for bit, which a shift / unshift
             # round trip through 'points' cannot guarantee
-            group.create_dataset('amd_points', data=bound.points,
+            group.create_dataset('amd_points', data=raw,
                                  maxshape=(None, bound.n_dim))
         group.attrs['n_sample'] = bound.n_sample
         group.attrs['n_reject'] = bound.n_reject
@@ -169,12 +175,14 @@ def _queue_points(bound, pts):
 
 
 def update_bound(bound, group):
-    """bounds/union.py:374-385, bounds/nautilus.py:328-342."""
+    """bounds/union.py:374-385, bounds/nautilus.py:328-342.  The queue is
+    read first: that lands a refill in flight, and the counters (the
+    envelope's included) and the stream written here are those behind it."""
+    pts = _file_points(bound)
     group.attrs['n_sample'] = bound.n_sample
     group.attrs['n_reject'] = bound.n_reject
     if isinstance(bound, nb.NautilusBound):
         update_bound(bound.outer_bound, group['outer_bound'])
-    pts = _file_points(bound)
     group['points'].resize(pts.shape)
     group['points'][...] = pts
     if 'amd_points' in group:
@@ -413,8 +421,10 @@ def write_sampler(sampler, filepath, overwrite=False):
     fstream.close()
 
 
-def write_shell_update(sampler, filepath, shell):
-    """sampler.py:1334-1377."""
+def write_shell_update(sampler, filepath, shell, landed=()):
+    """sampler.py:1334-1377.  ``landed``: indices of further bounds whose
+    state has moved since the file was written (a refill launched ahead of
+    time has landed in them); their entries are brought up to date too."""
     if shell < 0:
         shell = len(sampler.bounds) + shell
     fstream = h5py().File(Path(filepath), 'r+')
@@ -434,12 +444,13 @@ def write_shell_update(sampler, filepath, shell):
         if val is not None:
             group[key].resize(val.shape)
             group[key][...] = val
-    if isinstance(sampler.bounds[shell], nb.NautilusBound):
-        update_bound(sampler.bounds[shell],
-                     fstream['bound_{}'.format(shell)])
-    else:
-        _write_stream(sampler.bounds[shell],
-                      fstream['bound_{}'.format(shell)])
+    for index in sorted({shell} | set(landed)):
+        if isinstance(sampler.bounds[index], nb.NautilusBound):
+            update_bound(sampler.bounds[index],
+                         fstream['bound_{}'.format(index)])
+        else:
+            _write_stream(sampler.bounds[index],
+                          fstream['bound_{}'.format(index)])
     _write_rng(sampler, group)
     fstream.close()
 

@@ -1344,12 +1344,29 @@ class Sampler:
         """Write the sampler to an HDF5 file in the reference's layout
         (sampler.py:1253-1332)."""
         from . import io
+        self._land_refills()
         io.write_sampler(self, filepath, overwrite=overwrite)
 
     def write_shell_update(self, filepath, shell):
-        """sampler.py:1334-1377."""
+        """sampler.py:1334-1377, and the entry of every other bound in which
+        a refill launched ahead of time has landed since the file last saw
+        it (``_prefetch_next`` guesses the next shell: often not ``shell``)."""
         from . import io
-        io.write_shell_update(self, filepath, shell)
+        io.write_shell_update(self, filepath, shell, self._land_refills())
+
+    def _land_refills(self):
+        """Before a checkpoint is written: every refill in flight lands
+        (its Philox offset is taken, its rows and counts are not in yet -- a
+        file written now would hold neither the state before the launch nor
+        the one after it).  Returns the indices of the bounds whose state
+        has moved through a landing since the last checkpoint."""
+        moved = []
+        for i, bound in enumerate(self.bounds):
+            if hasattr(bound, 'land'):
+                bound.land()
+                if bound.__dict__.pop('_landed', False):
+                    moved.append(i)
+        return moved
 
     def shell_bound_occupation(self, fractional=True):
         """sampler.py:1223-1251."""

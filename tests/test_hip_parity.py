@@ -1117,6 +1117,48 @@ def test_refill_ahead_hands_out_the_same_points(dev):
     assert len(_PrefetchSlots.free) == free
 
 
+def test_refills_ahead_share_the_slots(dev):
+    """Five bounds launch a refill ahead of time before any of them is
+    asked -- one more than there are slots, so the fifth lands the oldest --
+    and are then asked in another order, each behind the synchronous refill
+    launches of the ones before it: the rows a refill in flight keeps in its
+    slot's buffer are not touched by the scratch buffers the launches in
+    between share, every bound hands out what a twin that never launched
+    ahead hands out, and every proposal is counted."""
+    from nautilus_amd.bounds import _PrefetchSlots
+    for owner, _ in list(_PrefetchSlots.owners):   # left by earlier tests
+        if owner.__dict__.get('_pending') is not None:
+            owner._land_pending()
+    assert len(_PrefetchSlots.free) == _PrefetchSlots.N_SLOTS
+    g = load_golden('nautilusbound_D4')
+    n_bounds = _PrefetchSlots.N_SLOTS + 1
+    asks = [3000 + 700 * i for i in range(n_bounds)]
+    ahead = [_product_bound(g, 200 + i) for i in range(n_bounds)]
+    twins = [_product_bound(g, 200 + i) for i in range(n_bounds)]
+    for b, n in zip(ahead, asks):
+        assert b.prefetch(n) is True
+    # the fifth acquire landed the oldest; the others are still in flight
+    assert [b.__dict__.get('_pending') is not None for b in ahead] == \
+        [False] + [True] * _PrefetchSlots.N_SLOTS
+    assert len(ahead[0]._queue(land=False)) > 0
+    assert _PrefetchSlots.free == []
+    got = {}
+    for i in (3, 0, 4, 1, 2):
+        got[i] = ahead[i].sample_device(asks[i]).clone()
+        assert ahead[i].__dict__.get('_pending') is None
+    assert len(_PrefetchSlots.free) == _PrefetchSlots.N_SLOTS
+    assert _PrefetchSlots.owners == []
+    for i, (b, t) in enumerate(zip(ahead, twins)):
+        assert torch.equal(got[i], t.sample_device(asks[i]))
+        # The launch issued ahead is the first launch of the twin's refill
+        # (same counters, same request, so the same size), and the refill
+        # loop goes on from the same state: no surplus launch, equal counts.
+        for x, y in ((b, t), (b.outer_bound, t.outer_bound)):
+            assert (x.n_sample, x.n_reject) == (y.n_sample, y.n_reject)
+        assert b._stream.offset == t._stream.offset
+        assert b.outer_bound.n_sample == b._stream.offset   # every proposal
+
+
 def test_shell_exclusion_and_association(dev, nautilus_d4, neural_d4):
     """sampler.py:797-798 and 1213-1219 over a list of nested bounds."""
     import torch

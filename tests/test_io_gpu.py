@@ -71,6 +71,14 @@ def test_bounds_round_trip(name, sync):
         assert b.log_v == r.log_v
 
 
+def _periodic_cloud():
+    """Points crowded around the seam of a periodic first dimension."""
+    pts = np.random.default_rng(3).random((1500, 2))
+    pts[:, 0] = (0.95 + 0.04 * np.random.default_rng(4).normal(size=1500)) % 1
+    log_l = -((pts[:, 0] - 0.95 + 0.5) % 1 - 0.5)**2 - (pts[:, 1] - 0.5)**2
+    return pts, log_l
+
+
 def test_periodic_bound_is_stored_in_the_reference_frame():
     """bounds/nautilus.py:239-243: the reference keeps the queued points of a
     NautilusBound in the SHIFTED frame and undoes the shift when it hands
@@ -79,9 +87,7 @@ def test_periodic_bound_is_stored_in_the_reference_frame():
     back in the sampler frame."""
     import nautilus_amd.bounds as nb
     rng = np.random.default_rng(0)
-    pts = np.random.default_rng(3).random((1500, 2))
-    pts[:, 0] = (0.95 + 0.04 * np.random.default_rng(4).normal(size=1500)) % 1
-    log_l = -((pts[:, 0] - 0.95 + 0.5) % 1 - 0.5)**2 - (pts[:, 1] - 0.5)**2
+    pts, log_l = _periodic_cloud()
     b = nb.NautilusBound.compute(pts, log_l, np.median(log_l), np.log(0.5),
                                  n_networks=0, periodic=np.arange(1), rng=rng)
     assert b.shift is not None
@@ -136,6 +142,289 @@ def test_sampler_resume_is_exact(tmp_path, blobs, n_like_max, discard,
         a.write(str(tmp_path / 'run.txt'))
     with pytest.raises(RuntimeError):
         a.write(path)
+
+
+# ---------------------------------------------------------------------------
+# checkpoints written while a prefetched refill is in flight
+# (``_RejectionSampler.prefetch``: the Philox offset has advanced, the rows
+# and the volume counters land with the next look at the queue)
+# ---------------------------------------------------------------------------
+
+def _pending(bound):
+    return bound.__dict__.get('_pending') is not None
+
+
+def _bound_with_queue(kind):
+    """A sampling bound that has handed out 50 points: counters and queue
+    are non-trivial, nothing is in flight."""
+    import nautilus_amd.bounds as nb
+    rng = np.random.default_rng(0)
+    if kind == 'periodic':
+        pts, log_l = _periodic_cloud()
+        b = nb.NautilusBound.compute(pts, log_l, np.median(log_l),
+                                     np.log(0.5), n_networks=0,
+                                     periodic=np.arange(1), rng=rng)
+        assert b.shift is not None
+    else:
+        pts = _cloud()
+        log_l = -np.linalg.norm(pts - 0.5, axis=1)
+        if kind == 'Union':
+            b = nb.Union.compute(pts[log_l > np.median(log_l)], rng=rng)
+        else:
+            b = nb.NautilusBound.compute(pts, log_l, np.median(log_l),
+                                         np.log(0.5), n_networks=1, rng=rng)
+    b.sample(50)
+    assert not _pending(b)
+    return b
+
+
+def _counter_owners(x, y):
+    """(bound, bound) pairs whose volume counters / streams are compared:
+    the bounds themselves and their sampling envelopes."""
+    pairs = [(x, y)]
+    if hasattr(x, 'outer_bound'):
+        pairs.append((x.outer_bound, y.outer_bound))
+    return pairs
+
+
+def _assert_same_sampling_state(x, y):
+    assert type(x) is type(y)
+    for p, q in _counter_owners(x, y):
+        if hasattr(p, 'n_sample'):
+            assert (p.n_sample, p.n_reject) == (q.n_sample, q.n_reject)
+        assert (p._stream.seed, p._stream.offset) == \
+            (q._stream.seed, q._stream.offset)
+        if hasattr(p, 'points'):
+            assert np.array_equal(p.points, q.points)
+
+
+@pytest.mark.parametrize('route', ['write', 'update'])
+@pytest.mark.parametrize('kind', ['Union', 'NautilusBound', 'periodic'])
+def test_bound_written_with_a_refill_in_flight(kind, route):
+    """``write`` / ``update`` of a bare bound while a prefetched refill is
+    in flight: the refill lands first, and the file holds the counters, the
+    stream position and the queue of one and the same moment -- the bound
+    that is read back has the volume of the one that was written and goes
+    on drawing the same points."""
+    from nautilus_amd import io
+    b = _bound_with_queue(kind)
+    group = fake_h5py.Group()
+    if route == 'update':
+        b.write(group)                   # nothing in flight yet
+    n_before = len(b.points)
+    assert b.prefetch(60000) is True
+    assert _pending(b)
+    if route == 'write':
+        b.write(group)
+    else:
+        b.update(group)
+    assert not _pending(b)
+    assert len(b.points) > n_before
+    assert int(group.attrs['n_sample']) == b.n_sample
+    assert int(group.attrs['n_reject']) == b.n_reject
+    if hasattr(b, 'outer_bound'):
+        outer = group['outer_bound']
+        assert int(outer.attrs['n_sample']) == b.outer_bound.n_sample
+        assert int(outer.attrs['n_reject']) == b.outer_bound.n_reject
+    assert int(group.attrs['amd_philox_offset']) == b._stream.offset
+    assert np.array_equal(np.array(group['points']), io._file_points(b))
+    assert ('amd_points' in group) == (kind == 'periodic')
+    if 'amd_points' in group:
+        assert np.array_equal(np.array(group['amd_points']), b.points)
+
+    r = type(b).read(group, rng=np.random.default_rng(1))
+    _assert_same_sampling_state(r, b)
+    assert r.log_v == b.log_v
+    # more than the queue holds, so fresh proposals are drawn
+    k = len(b.points) + 5000
+    assert np.array_equal(b.sample(k), r.sample(k))
+    _assert_same_sampling_state(r, b)
+
+
+def _gauss2():
+    from nautilus_amd import GaussianLikelihood
+    return GaussianLikelihood(np.full(2, 0.5), np.eye(2) * 0.04)
+
+
+# (likelihood, blobs, n_networks, periodic)
+_RESUME_CASES = {
+    'plain': ('host', False, 0, None),
+    'blobs': ('host', True, 0, None),
+    'net': ('host', False, 1, None),
+    'net_blobs': ('host', True, 1, None),
+    'net_periodic': ('host', False, 1, np.arange(1)),
+    'device': ('device', False, 1, None)}
+
+
+def _resume_sampler(case, path, **kwargs):
+    from nautilus_amd import Sampler, unit_prior
+    kind, blobs, n_networks, periodic = _RESUME_CASES[case]
+    kw = dict(n_dim=2, n_live=100, n_networks=n_networks, periodic=periodic,
+              filepath=path, **kwargs)
+    if kind == 'device':
+        return Sampler(unit_prior, _gauss2(), vectorized=True, **kw), blobs
+    return Sampler(lambda u: u, _flat_blob if blobs else _flat, **kw), blobs
+
+
+def _put_refill_in_flight(bound):
+    if not _pending(bound):
+        assert bound.prefetch(len(bound._queue(land=False)) + 5000) is True
+    assert _pending(bound)
+
+
+def _assert_resumed_like_written(a, b):
+    """``b`` was read from the checkpoint ``a`` wrote last: every bound of
+    it is in the state ``a``'s is in (reading ``a``'s queue lands what is
+    still in flight there), and the evidence rests on the same volumes."""
+    assert len(a.bounds) == len(b.bounds)
+    for x, y in zip(a.bounds, b.bounds):
+        _assert_same_sampling_state(x, y)
+    assert a.log_z == b.log_z
+    # (nan: a shell nothing was drawn for yet)
+    assert np.array_equal(a.shell_log_v, b.shell_log_v, equal_nan=True)
+
+
+def _assert_same_continuation(a, b, blobs, f_live):
+    a.run(f_live=f_live, n_eff=5000)
+    b.run(f_live=f_live, n_eff=5000)
+    for x, y in zip(a.posterior(return_blobs=blobs),
+                    b.posterior(return_blobs=blobs)):
+        assert np.array_equal(x, y)
+    assert a.log_z == b.log_z and a.n_like == b.n_like
+
+
+@pytest.mark.parametrize('target', ['shell', 'other'])
+@pytest.mark.parametrize('case', sorted(_RESUME_CASES))
+def test_shell_update_with_a_refill_in_flight(tmp_path, case, target):
+    """One step of ``run()`` in the sampling phase -- ``add_samples(shell)``,
+    then ``write_shell_update(shell)`` -- with a refill in flight on the
+    bound of that shell, or on another bound (a wrong guess of
+    ``_prefetch_next``): the resumed sampler is in the state of the one that
+    wrote the file, and both continue alike."""
+    path = str(tmp_path / 'run.hdf5')
+    a, blobs = _resume_sampler(case, path, resume=False, seed=0)
+    # n_eff = 0: until the exploration phase has ended
+    assert a.run(f_live=0.05, n_eff=0) is True
+    assert a.explored and len(a.bounds) >= 3
+    shell = max(1, a._next_shell())
+    a.add_samples(shell)
+    others = [i for i in range(1, len(a.bounds)) if i != shell]
+    index = shell if target == 'shell' else others[-1]
+    _put_refill_in_flight(a.bounds[index])
+    a.write_shell_update(path, shell)
+    b, _ = _resume_sampler(case, path, resume=True)
+    _assert_resumed_like_written(a, b)
+    _assert_same_continuation(a, b, blobs, 0.05)
+
+
+@pytest.mark.parametrize('case', ['plain', 'net_blobs', 'net_periodic'])
+def test_full_write_with_a_refill_in_flight(tmp_path, case):
+    """Exploration with a host likelihood: the refill of the last bound is
+    launched while the CPU evaluates the batch (``after_fetch``), so the
+    complete ``write`` that follows ``add_bound()`` meets it in flight."""
+    path = str(tmp_path / 'run.hdf5')
+    a, blobs = _resume_sampler(case, path, resume=False, seed=0)
+    assert a.run(f_live=0.01, n_like_max=600) is False
+    assert not a.explored and len(a.bounds) >= 2
+    last = a.bounds[-1]
+    _put_refill_in_flight(last)
+    a.add_bound()                                  # what run() does next
+    a.n_update_iter = 0
+    a.n_like_iter = 0
+    assert _pending(last)
+    a.write(path, overwrite=True)
+    assert not _pending(last)
+    b, _ = _resume_sampler(case, path, resume=True)
+    _assert_resumed_like_written(a, b)
+    _assert_same_continuation(a, b, blobs, 0.01)
+
+
+# proposals per refill launch in test_sampler_resume_with_refills_in_flight
+# (bounds.MIN_DRAW / MAX_DRAW): a batch of 100 points asks its bound for a few
+# hundred, so with launches this small nearly every batch needs a refill
+SMALL_MIN_DRAW, SMALL_MAX_DRAW = 64, 1024
+
+
+def _count_checkpoints_in_flight(monkeypatch):
+    """Wrap ``Sampler.write`` / ``write_shell_update`` at the class: the
+    checkpoints entered with a refill in flight, seen before anything
+    lands."""
+    from nautilus_amd import Sampler
+    counts = dict(shell=0, other=0, full=0)
+    real_write, real_update = Sampler.write, Sampler.write_shell_update
+
+    def in_flight(s):
+        return [i for i, bound in enumerate(s.bounds) if _pending(bound)]
+
+    def write(self, *args, **kwargs):
+        counts['full'] += bool(in_flight(self))
+        return real_write(self, *args, **kwargs)
+
+    def write_shell_update(self, filepath, shell):
+        own = shell % len(self.bounds)
+        flying = in_flight(self)
+        counts['shell'] += own in flying
+        counts['other'] += any(i != own for i in flying)
+        return real_update(self, filepath, shell)
+
+    monkeypatch.setattr(Sampler, 'write', write)
+    monkeypatch.setattr(Sampler, 'write_shell_update', write_shell_update)
+    return counts
+
+
+def _guess_both_ways(monkeypatch):
+    """In the sampling phase every other guess of ``_predict_next_shell``
+    names the bound of the shell that was just sampled; the guesses in
+    between are the sampler's own.  (A run this small has two bounds, and
+    its own guesses were seen to leave the checkpoints with a refill in
+    flight on ``bounds[shell]`` out altogether when there is a network; a
+    guess only decides the order of the work.)  A function of the restored
+    state: the resumed sampler guesses like the one that wrote the file."""
+    from nautilus_amd import Sampler
+    real = Sampler._predict_next_shell
+
+    def predict(self, shell, n_new):
+        own = shell % len(self.bounds)
+        if self.explored and own > 0 and \
+                (self.n_like // self.n_batch) % 2 == 0:
+            return own
+        return real(self, shell, n_new)
+
+    monkeypatch.setattr(Sampler, '_predict_next_shell', predict)
+
+
+@pytest.mark.parametrize('blobs,n_like_max,discard,n_networks,periodic', [
+    (False, np.inf, False, 0, None), (True, 500, True, 0, None),
+    (False, 500, True, 1, np.arange(1)), (True, np.inf, False, 1, None)])
+def test_sampler_resume_with_refills_in_flight(tmp_path, monkeypatch, blobs,
+                                               n_like_max, discard,
+                                               n_networks, periodic):
+    """``test_sampler_resume_is_exact`` with refill launches so small that
+    ``run()`` itself keeps writing checkpoints while a refill is in flight,
+    on the bound of the shell it updates and on others."""
+    from nautilus_amd import Sampler, bounds
+    monkeypatch.setattr(bounds, 'MIN_DRAW', SMALL_MIN_DRAW)
+    monkeypatch.setattr(bounds, 'MAX_DRAW', SMALL_MAX_DRAW)
+    _guess_both_ways(monkeypatch)
+    counts = _count_checkpoints_in_flight(monkeypatch)
+    path = str(tmp_path / 'run.hdf5')
+    like = _flat_blob if blobs else _flat
+    kw = dict(n_dim=2, n_live=100, n_networks=n_networks, periodic=periodic,
+              filepath=path)
+    a = Sampler(lambda u: u, like, resume=False, seed=0, **kw)
+    a.run(f_live=0.45, n_eff=1000, n_like_max=n_like_max,
+          discard_exploration=discard)
+    b = Sampler(lambda u: u, like, resume=True, **kw)
+    assert a.log_z == b.log_z and a.n_like == b.n_like
+    _assert_resumed_like_written(a, b)
+    a.run(f_live=0.45, n_eff=5000, discard_exploration=discard)
+    b.run(f_live=0.45, n_eff=5000, discard_exploration=discard)
+    print('checkpoints entered with a refill in flight:', counts)
+    for x, y in zip(a.posterior(return_blobs=blobs),
+                    b.posterior(return_blobs=blobs)):
+        assert np.array_equal(x, y)
+    assert a.log_z == b.log_z and a.n_like == b.n_like
+    assert counts['shell'] >= 1 and counts['other'] >= 1, counts
 
 
 # ---------------------------------------------------------------------------
