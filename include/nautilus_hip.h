@@ -471,6 +471,43 @@ int nb_chi2_loglike(const nb_chi2* h, const double* model_dev, int64_t ld,
                     int64_t n, double* out_dev, void* stream);
 int nb_chi2_destroy(nb_chi2* h);
 
+/* Poisson likelihood of binned counts (the user-side callable of
+ * sampler.py:863-873 for a model prediction m(theta) of the rates in P bins
+ * with observed counts k), one streaming launch that reads every model row
+ * once:  mu_ij = exposure_j m_ij + background_j,
+ *   out_dev[i] = log_const - sum_j D(mu_ij, k_j),   D(mu, 0) = mu,
+ *   D(mu, k) = k (t - lg),  t = (mu - k) (1 / k),
+ *              lg = log1p(t) if |t| < 1/2 else log(mu (1 / k)):
+ * the deviance form, every term >= 0.  With log_const = sum_j [k log k - k -
+ * lgamma(k + 1)] the result is sum_j log Poisson(k_j | mu_ij); with 0 it is
+ * -1/2 of Cash's C statistic.
+ * counts [P] finite and >= 0 (need not be integers); exposure [P] > 0 or NULL
+ * (= 1); background [P] >= 0 or NULL (= 0): host arrays, read here and
+ * uploaded once with 1 / k.  NB_ERR_ARG: n_data outside
+ * 1..NB_POISSON_MAX_DATA, NULL counts, a non-finite or negative count, a
+ * positive count so small that 1 / k overflows (below about 5.6e-309), a
+ * non-positive or non-finite exposure, a negative or non-finite background, a
+ * non-finite log_const.
+ * nb_poisson_loglike (sampler.py:863-873) only launches, on the caller's
+ * stream (one handle serves any number of streams): row i of the model is the
+ * n_data doubles at model_dev + i * ld (NB_ERR_ARG for ld < n_data with n > 1,
+ * and for a NULL pointer with n > 0).  mu = 0 in a bin with k > 0 makes the
+ * row -inf; a negative, NaN or infinite mu makes it NaN (and wins over -inf);
+ * neither changes another row.  The bits of a row depend on neither n, its
+ * position in the batch, ld, the stream nor the grid.  n = 0 returns NB_OK
+ * without a launch.  (mu / k must stay below the float64 maximum: with a count
+ * under 1e-290 a finite mu can overflow mu (1 / k), and the row is NaN.)
+ *  nb_poisson_destroy frees the handle of the same callable
+ * (sampler.py:863-873); NULL is NB_OK.                                      */
+typedef struct nb_poisson nb_poisson;
+#define NB_POISSON_MAX_DATA (1 << 20)
+int nb_poisson_create(int32_t n_data, const double* counts,
+                      const double* exposure, const double* background,
+                      double log_const, nb_poisson** out);
+int nb_poisson_loglike(const nb_poisson* h, const double* model_dev,
+                       int64_t ld, int64_t n, double* out_dev, void* stream);
+int nb_poisson_destroy(nb_poisson* h);
+
 
 /* Two-stage evaluation of bounds with several outer members, several neural
  * bounds, or of lists of bounds (bounds/union.py:285-289, 316-319;

@@ -18,6 +18,7 @@ _LAZY = {
     'GaussianLikelihood': 'likelihoods',
     'GaussianMixtureLikelihood': 'likelihoods', 'unit_prior': 'likelihoods',
     'GaussianDataLikelihood': 'likelihoods',
+    'PoissonDataLikelihood': 'likelihoods',
     'RosenbrockLikelihood': 'likelihoods', 'FunnelLikelihood': 'likelihoods',
 }
 

@@ -1499,6 +1499,87 @@ int nb_chi2_loglike(const nb_chi2* h, const double* model, int64_t ld,
                         as_stream(stream));
 }
 
+// Counts, their reciprocals, exposure and background for nb_poisson.hip,
+// uploaded once.
+struct nb_poisson {
+  double* dev = nullptr;
+  int n_data = 0;
+  double log_const = 0.0;
+};
+
+int nb_poisson_create(int32_t n_data, const double* counts,
+                      const double* exposure, const double* background,
+                      double log_const, nb_poisson** out) {
+  if (out == nullptr || counts == nullptr || n_data < 1 ||
+      n_data > NB_POISSON_MAX_DATA || !std::isfinite(log_const)) {
+    nb_set_error("bad Poisson likelihood arguments (n_data 1..%d, counts, a "
+                 "finite log_const)", NB_POISSON_MAX_DATA);
+    return NB_ERR_ARG;
+  }
+  *out = nullptr;
+  const size_t p = (size_t)n_data;
+  std::vector<double> host(4 * p);
+  for (size_t j = 0; j < p; ++j) {
+    const double k = counts[j];
+    const double e = exposure != nullptr ? exposure[j] : 1.0;
+    const double b = background != nullptr ? background[j] : 0.0;
+    if (!std::isfinite(k) || k < 0.0) {
+      nb_set_error("count %zu must be finite and not negative", j);
+      return NB_ERR_ARG;
+    }
+    if (k > 0.0 && !std::isfinite(1.0 / k)) {
+      nb_set_error("count %zu is positive but too small: 1 / k is not finite",
+                   j);
+      return NB_ERR_ARG;
+    }
+    if (!std::isfinite(e) || !(e > 0.0)) {
+      nb_set_error("exposure %zu must be positive and finite", j);
+      return NB_ERR_ARG;
+    }
+    if (!std::isfinite(b) || b < 0.0) {
+      nb_set_error("background %zu must be finite and not negative", j);
+      return NB_ERR_ARG;
+    }
+    host[j] = k;
+    host[p + j] = k > 0.0 ? 1.0 / k : 0.0;
+    host[2 * p + j] = e;
+    host[3 * p + j] = b;
+  }
+  nb_poisson* c = new nb_poisson;
+  c->n_data = n_data;
+  c->log_const = log_const;
+  const size_t bytes = host.size() * sizeof(double);
+  hipError_t e = hipMalloc((void**)&c->dev, bytes);
+  if (e == hipSuccess)
+    e = hipMemcpy(c->dev, host.data(), bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    nb_set_error("Poisson likelihood upload failed: %s", hipGetErrorString(e));
+    if (c->dev != nullptr) (void)hipFree(c->dev);
+    delete c;
+    return NB_ERR_HIP;
+  }
+  *out = c;
+  return NB_OK;
+}
+
+int nb_poisson_destroy(nb_poisson* h) {
+  if (h == nullptr) return NB_OK;
+  (void)hipFree(h->dev);
+  delete h;
+  return NB_OK;
+}
+
+int nb_poisson_loglike(const nb_poisson* h, const double* model, int64_t ld,
+                       int64_t n, double* out, void* stream) {
+  if (h == nullptr || n < 0 || (n > 1 && ld < h->n_data) ||
+      (n > 0 && (model == nullptr || out == nullptr))) {
+    nb_set_error("bad Poisson likelihood arguments (ld >= n_data)");
+    return NB_ERR_ARG;
+  }
+  return nb_launch_poisson(h->dev, h->n_data, model, ld, n, h->log_const, out,
+                           as_stream(stream));
+}
+
 int nb_live_append(const double* log_l, int64_t n, const double* thr,
                    double* pool, int32_t* pool_n, int32_t capacity,
                    int32_t* overflow, void* stream) {

@@ -127,6 +127,12 @@ int nb_launch_chi2_diag(const double* blob, int n_data, const double* model,
                         long long ld, long long n, double log_norm,
                         double* out, hipStream_t stream);
 
+// Poisson likelihood of binned counts (nb_poisson.hip).  The table is four
+// arrays of P doubles: k, 1 / k (0 where k = 0), exposure, background.
+int nb_launch_poisson(const double* tab, int n_data, const double* model,
+                      long long ld, long long n, double log_const,
+                      double* out, hipStream_t stream);
+
 // One (bound, neural bound) group of a two-stage query (nb_cand.hip ->
 // nb_eval_fast.hip, BATCH): built on the host when a bound / a bound list is
 // created, read by the second stage per 128-point pass.

@@ -672,6 +672,53 @@ class Chi2Table:
         return out
 
 
+class PoissonTable:
+    """Device-resident bins of a Poisson likelihood (``nb_poisson_create``):
+    ``counts`` (P,) >= 0, ``exposure`` (P,) > 0 (None = 1) and ``background``
+    (P,) >= 0 (None = 0), with ``log_const`` added to every result.  Uploaded
+    once; every ``loglike`` is one launch on the current stream."""
+
+    def __init__(self, counts, exposure=None, background=None, log_const=0.0):
+        self._lib = lib = _lib.load()
+        counts = _f64(counts)
+        if counts.ndim != 1:
+            raise ValueError('counts must be one-dimensional')
+        self.n_data = p = len(counts)
+        if exposure is not None:
+            exposure = _f64(exposure)
+            if exposure.shape != (p,):
+                raise ValueError('exposure must have shape (%d,)' % p)
+        if background is not None:
+            background = _f64(background)
+            if background.shape != (p,):
+                raise ValueError('background must have shape (%d,)' % p)
+        h = C.c_void_p()
+        _lib.check(lib.nb_poisson_create(
+            p, _dp(counts), None if exposure is None else _dp(exposure),
+            None if background is None else _dp(background),
+            float(log_const), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, '_h', None)
+        if h:
+            self._lib.nb_poisson_destroy(h)
+            self._h = None
+
+    def loglike(self, model, ld=None):
+        """log L of the rows of the cuda float64 tensor ``model`` (n, P),
+        read in place: its rows may be strided (``stride(1) == 1``,
+        ``stride(0) >= P``).  ``ld`` overrides the row stride (in doubles)
+        the tensor reports."""
+        n = model.shape[0]
+        if ld is None:
+            ld = model.stride(0) if n > 1 else self.n_data
+        out = torch.empty(n, dtype=torch.float64, device=model.device)
+        _lib.check(self._lib.nb_poisson_loglike(
+            self._h, _ptr(model), ld, n, _ptr(out), _stream()))
+        return out
+
+
 
 def gmm_fit(x, n_init=10, seed=0, tol=1e-3, reg_covar=1e-6, max_iter=100,
             init_labels=None):

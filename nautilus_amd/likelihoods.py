@@ -345,6 +345,225 @@ class GaussianDataLikelihood:
         return state
 
 
+N_COUNTS_MAX = 1 << 20             # NB_POISSON_MAX_DATA of nautilus_hip.h
+
+
+def poisson_log_const(counts):
+    """Per bin  k log k - k - lgamma(k + 1)  (0 for k = 0), the part of the
+    Poisson log-probability that the deviance leaves out.  From k = 16 on it
+    is the Stirling series -1/2 log(2 pi k) - 1/(12 k) + 1/(360 k^3) -
+    1/(1260 k^5) + ..., not the difference of two numbers of size k log k;
+    the series runs to the k^-11 term, which leaves less than 2e-18 at
+    k = 16.  Below 16 the direct expression is formed in ``np.longdouble``
+    (lgamma by the same series after shifting the argument past 16) and
+    rounded once: within 0.2 eps max(1, |C|) where long double is the 80-bit
+    type (x86-64 Linux).  Where ``np.longdouble`` is float64 the same code
+    runs in float64 and errs by up to about 4 eps |C| for k between 2 and
+    16 (a RuntimeWarning says so once per call)."""
+    k = np.asarray(counts, float)
+    out = np.zeros(k.shape)
+
+    def series(x):
+        # sum_n B_2n / (2n (2n - 1) x^(2n - 1)), n = 1 .. 6
+        y = 1 / (x * x)
+        return (1 / x) * (1 / x.dtype.type(12) + y * (
+            -1 / x.dtype.type(360) + y * (1 / x.dtype.type(1260) + y * (
+                -1 / x.dtype.type(1680) + y * (1 / x.dtype.type(1188) - y * (
+                    x.dtype.type(691) / x.dtype.type(360360)))))))
+
+    big = k >= 16
+    kb = k[big]
+    out[big] = -0.5 * np.log(2 * np.pi * kb) - series(kb)
+    small = (k > 0) & ~big
+    if np.any(small) and np.finfo(np.longdouble).eps >= np.finfo(float).eps:
+        import warnings
+        warnings.warn('np.longdouble is float64 here: poisson_log_const is '
+                      'accurate to about 4 eps |C| only below k = 16',
+                      RuntimeWarning)
+    ks = k[small].astype(np.longdouble)
+    # lgamma(k + 1) = stirling(k + 17) - sum_{i = 1 .. 16} log(k + i)
+    z = ks + 17
+    two_pi = 2 * np.arccos(np.longdouble(-1))
+    lg = (z - 0.5) * np.log(z) - z + 0.5 * np.log(two_pi) + series(z)
+    for i in range(1, 17):
+        lg = lg - np.log(ks + i)
+    out[small] = (ks * np.log(ks) - ks - lg).astype(float)
+    return out
+
+
+class PoissonDataLikelihood:
+    """Poisson likelihood of counts in bins:  log L(theta) = sum_j log
+    Poisson(k_j | mu_j(theta)),  mu_j = exposure_j m_j(theta) + background_j.
+
+    ``model`` takes the (n, n_dim) batch of points as a torch tensor and
+    returns the (n, P) float64 predictions on the same device; ``counts``
+    holds the P observed counts k_j >= 0 (they need not be integers, as in an
+    Asimov data set; a positive count must have a finite reciprocal, and
+    mu / k must stay below the float64 maximum -- with counts under 1e-290 a
+    finite mu can overflow it and the row is NaN); ``exposure`` (P positive numbers, default 1) and
+    ``background`` (P numbers >= 0, default 0) map the model onto expected
+    counts.  P is at most 2^20.
+
+    The sum is evaluated in the deviance form
+
+        log L = log_const - sum_j D(mu_j, k_j),       D(mu, 0) = mu,
+        D(mu, k) = k (t - lg),   t = (mu - k) (1 / k),
+                   lg = log1p(t) if |t| < 1/2 else log(mu (1 / k)),
+
+    whose terms are all >= 0: nothing cancels, unlike in k log mu - mu for
+    large counts.  ``log_const = sum_j [k_j log k_j - k_j - lgamma(k_j + 1)]``
+    (``poisson_log_const``) makes the result the sum of
+    ``scipy.stats.poisson.logpmf(k, mu)``; with ``normalised=False`` it is 0
+    and the result is -1/2 of Cash's C statistic (Cash 1979).
+
+    A call evaluates the model and then runs the fused kernel
+    ``nb_poisson_loglike`` -- one streaming launch on the current stream that
+    reads every model row once.  ``from_model`` is the second half alone; it
+    reads a cuda tensor whose rows are strided (``stride(1) == 1``,
+    ``stride(0) >= P``, such as a column slice of a wider tensor) in place
+    and copies anything else to contiguous.  ``numpy`` / ``numpy_from_model``
+    are the pure-numpy twins, ``numpy_deviance`` the matrix of the D.
+
+    In row i,  mu = 0 in a bin with k > 0 makes ``out[i]`` -inf (mu = 0 with
+    k = 0 contributes 0); a negative, NaN or infinite mu makes it NaN, also
+    next to a -inf bin.  Neither changes a bit of any other row."""
+
+    device = True
+
+    def __init__(self, model, counts, *, exposure=None, background=None,
+                 normalised=True):
+        if not callable(model):
+            raise ValueError('model must be callable')
+        self.model = model
+        counts = np.asarray(counts, float)
+        if counts.ndim != 1 or len(counts) < 1:
+            raise ValueError('counts must be a vector of at least one number')
+        if len(counts) > N_COUNTS_MAX:
+            raise ValueError('at most %d bins are supported, not %d' %
+                             (N_COUNTS_MAX, len(counts)))
+        if not np.all(np.isfinite(counts)) or not np.all(counts >= 0):
+            raise ValueError('counts must be finite and not negative')
+        with np.errstate(divide='ignore', over='ignore'):
+            if not np.all(np.isfinite(1.0 / counts[counts > 0])):
+                raise ValueError('a positive count is too small: 1 / k is '
+                                 'not finite')
+        self.counts = counts.copy()
+        self.n_data = p = len(counts)
+        if exposure is None:
+            self.exposure = np.ones(p)
+        else:
+            exposure = np.asarray(exposure, float)
+            if exposure.shape != (p,) or \
+                    not np.all(np.isfinite(exposure)) or \
+                    not np.all(exposure > 0):
+                raise ValueError('exposure must be %d positive finite numbers'
+                                 % p)
+            self.exposure = exposure.copy()
+        if background is None:
+            self.background = np.zeros(p)
+        else:
+            background = np.asarray(background, float)
+            if background.shape != (p,) or \
+                    not np.all(np.isfinite(background)) or \
+                    not np.all(background >= 0):
+                raise ValueError('background must be %d finite numbers that '
+                                 'are not negative' % p)
+            self.background = background.copy()
+        # 1 / k as the device table holds it: 0 where k = 0
+        self._inv_counts = np.zeros(p)
+        np.divide(1.0, counts, out=self._inv_counts, where=counts > 0)
+        self.log_const = (float(np.sum(poisson_log_const(counts)))
+                          if normalised else 0.0)
+        if not np.isfinite(self.log_const):
+            raise ValueError('counts are too large: log_const is not finite')
+        self._tables = {}
+
+    def _table(self):
+        """The device handle of the current device, built on first use."""
+        dev = torch.cuda.current_device()
+        if dev not in self._tables:
+            self._tables[dev] = device.PoissonTable(
+                self.counts, self.exposure, self.background,
+                log_const=self.log_const)
+        return self._tables[dev]
+
+    def _check(self, m):
+        if m.ndim != 2 or m.shape[1] != self.n_data:
+            raise ValueError('the model output must have shape (n, %d), not '
+                             '%s' % (self.n_data, tuple(m.shape)))
+
+    def from_model(self, m):
+        """log L of the rows of an (n, P) float64 model output: a cuda tensor
+        in, a cuda tensor out; numpy in, numpy out."""
+        if isinstance(m, torch.Tensor):
+            if m.dtype != torch.float64:
+                raise ValueError('the model output must be float64, not %s' %
+                                 m.dtype)
+            self._check(m)
+            t = m if m.is_cuda else m.cuda()
+            p = self.n_data
+            in_place = (p == 1 or t.stride(1) == 1) and \
+                (t.shape[0] <= 1 or t.stride(0) >= p)
+            return self._table().loglike(t if in_place else t.contiguous())
+        m = np.asarray(m)
+        if m.dtype != np.float64:
+            raise ValueError('the model output must be float64, not %s' %
+                             m.dtype)
+        self._check(m)
+        t = torch.from_numpy(np.ascontiguousarray(m)).cuda()
+        return self._table().loglike(t).cpu().numpy()
+
+    def __call__(self, x):
+        if isinstance(x, torch.Tensor):
+            return self.from_model(self.model(x))
+        xs = device.as_device_points(x)
+        return self.from_model(self.model(xs)).cpu().numpy()
+
+    def numpy_deviance(self, m):
+        """The (n, P) terms D(mu_ij, k_j) of an (n, P) model output in pure
+        numpy, by the formulas of the class docstring: +inf where mu = 0 and
+        k > 0, NaN where mu is negative, NaN or infinite."""
+        m = np.asarray(m, float)
+        self._check(m)
+        k, ik = self.counts, self._inv_counts
+        with np.errstate(all='ignore'):
+            mu = self.exposure * m + self.background
+            fin = (mu >= 0) & (mu < np.inf)
+            pos = np.broadcast_to(k > 0, mu.shape)
+            live = fin & (mu > 0) & pos
+            t = np.where(live, (mu - k) * ik, 0.0)
+            small = np.abs(t) < 0.5
+            lg = np.where(small, np.log1p(np.where(small, t, 0.0)),
+                          np.log(np.where(small, 1.0, mu * ik)))
+            d = np.where(pos, k * (t - lg), mu)
+        d[fin & (mu == 0) & pos] = np.inf
+        d[~fin] = np.nan
+        return d
+
+    def numpy_from_model(self, m):
+        """Pure-numpy evaluation of an (n, P) model output (CPU baseline /
+        oracle runs / tests)."""
+        d = self.numpy_deviance(m)
+        flagged = ~np.isfinite(d)
+        out = self.log_const - np.sum(np.where(flagged, 0.0, d), axis=1)
+        out[np.any(np.isinf(d), axis=1)] = -np.inf
+        out[np.any(np.isnan(d), axis=1)] = np.nan
+        return out
+
+    def numpy(self, x):
+        """Pure-numpy twin of a call: the model runs on the CPU."""
+        x = np.atleast_2d(np.asarray(x, float))
+        m = self.model(torch.from_numpy(x))
+        if isinstance(m, torch.Tensor):
+            m = m.detach().cpu().numpy()
+        return self.numpy_from_model(m)
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state['_tables'] = {}
+        return state
+
+
 class RosenbrockLikelihood:
     """Rosenbrock function on x = low + (high - low) u (BASELINE config 3):
     log L = -sum_i [a (x_{i+1} - x_i^2)^2 + (1 - x_i)^2] --
