@@ -508,6 +508,46 @@ int nb_poisson_loglike(const nb_poisson* h, const double* model_dev,
                        int64_t ld, int64_t n, double* out_dev, void* stream);
 int nb_poisson_destroy(nb_poisson* h);
 
+/* The same Poisson likelihood behind a response matrix (the user-side callable
+ * of sampler.py:863-873 for a model that predicts K source-space quantities
+ * s(theta) -- fluxes in true-energy bins, template amplitudes -- which an
+ * instrument response or a set of templates R maps onto the P bins):
+ *   mu_ij = exposure_j sum_k R_jk s_ik + background_j,
+ *   out_dev[i] = log_const - sum_j D(mu_ij, k_j),
+ * D, log_const and the -inf / NaN rules those of nb_poisson_loglike.  One
+ * launch forms the mu on the fp64 matrix cores and feeds them straight into
+ * the deviance: the n x P matrix of the mu is never stored.
+ * counts, exposure, background as for nb_poisson_create; response [P rows of
+ * n_src doubles, ld_response doubles apart] any finite values (a negative
+ * entry is legal; a negative mu is NaN by the rule above): host arrays, read
+ * here; R is packed as zero-padded 16 x 16 operand tiles and uploaded once.
+ * NB_ERR_ARG: whatever nb_poisson_create refuses, n_src outside
+ * 1..NB_FOLD_MAX_SOURCE, ceil16(n_data) * ceil16(n_src) above
+ * NB_FOLD_MAX_RESPONSE doubles (128 MiB packed: 4096 x 4096, or 2^20 x 16),
+ * NULL response, ld_response < n_src, a non-finite response entry.  The sizes
+ * are checked before any array is read.
+ * nb_fold_poisson_loglike (sampler.py:863-873) only launches, on the caller's
+ * stream (one handle serves any number of streams): row i of the source values
+ * is the n_src doubles at src_dev + i * ld (NB_ERR_ARG for ld < n_src with
+ * n > 1, and for a NULL pointer with n > 0).  A NaN or infinite source value
+ * makes its row NaN, also where the response column it meets is all zeros, and
+ * changes no other row.  The bits of a row depend on P and K only: on neither
+ * n, its position in the batch, ld, the stream nor the grid.  n = 0 returns
+ * NB_OK without a launch.
+ *  nb_fold_poisson_destroy frees the handle of the same callable
+ * (sampler.py:863-873); NULL is NB_OK.                                      */
+typedef struct nb_fold_poisson nb_fold_poisson;
+#define NB_FOLD_MAX_SOURCE (1 << 20)
+#define NB_FOLD_MAX_RESPONSE (1 << 24)
+int nb_fold_poisson_create(int32_t n_data, int32_t n_src, const double* counts,
+                           const double* response, int64_t ld_response,
+                           const double* exposure, const double* background,
+                           double log_const, nb_fold_poisson** out);
+int nb_fold_poisson_loglike(const nb_fold_poisson* h, const double* src_dev,
+                            int64_t ld, int64_t n, double* out_dev,
+                            void* stream);
+int nb_fold_poisson_destroy(nb_fold_poisson* h);
+
 
 /* Two-stage evaluation of bounds with several outer members, several neural
  * bounds, or of lists of bounds (bounds/union.py:285-289, 316-319;

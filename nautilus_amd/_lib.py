@@ -171,6 +171,13 @@ _SIGNATURES = {
     'nb_poisson_loglike': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_int64, C.c_void_p, C.c_void_p]),
     'nb_poisson_destroy': (C.c_int, [C.c_void_p]),
+    'nb_fold_poisson_create': (C.c_int, [C.c_int32, C.c_int32, c_double_p,
+                                         c_double_p, C.c_int64, c_double_p,
+                                         c_double_p, C.c_double,
+                                         C.POINTER(C.c_void_p)]),
+    'nb_fold_poisson_loglike': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_int64, C.c_void_p, C.c_void_p]),
+    'nb_fold_poisson_destroy': (C.c_int, [C.c_void_p]),
     'nb_live_append': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_int32,
                                  C.c_void_p, C.c_void_p]),

@@ -1507,6 +1507,29 @@ struct nb_poisson {
   double log_const = 0.0;
 };
 
+// one bin of a Poisson table: false (and the error text) unless the count,
+// exposure and background are what nb_poisson_create documents
+static bool po_check_bin(size_t j, double k, double e, double b) {
+  if (!std::isfinite(k) || k < 0.0) {
+    nb_set_error("count %zu must be finite and not negative", j);
+    return false;
+  }
+  if (k > 0.0 && !std::isfinite(1.0 / k)) {
+    nb_set_error("count %zu is positive but too small: 1 / k is not finite",
+                 j);
+    return false;
+  }
+  if (!std::isfinite(e) || !(e > 0.0)) {
+    nb_set_error("exposure %zu must be positive and finite", j);
+    return false;
+  }
+  if (!std::isfinite(b) || b < 0.0) {
+    nb_set_error("background %zu must be finite and not negative", j);
+    return false;
+  }
+  return true;
+}
+
 int nb_poisson_create(int32_t n_data, const double* counts,
                       const double* exposure, const double* background,
                       double log_const, nb_poisson** out) {
@@ -1523,23 +1546,7 @@ int nb_poisson_create(int32_t n_data, const double* counts,
     const double k = counts[j];
     const double e = exposure != nullptr ? exposure[j] : 1.0;
     const double b = background != nullptr ? background[j] : 0.0;
-    if (!std::isfinite(k) || k < 0.0) {
-      nb_set_error("count %zu must be finite and not negative", j);
-      return NB_ERR_ARG;
-    }
-    if (k > 0.0 && !std::isfinite(1.0 / k)) {
-      nb_set_error("count %zu is positive but too small: 1 / k is not finite",
-                   j);
-      return NB_ERR_ARG;
-    }
-    if (!std::isfinite(e) || !(e > 0.0)) {
-      nb_set_error("exposure %zu must be positive and finite", j);
-      return NB_ERR_ARG;
-    }
-    if (!std::isfinite(b) || b < 0.0) {
-      nb_set_error("background %zu must be finite and not negative", j);
-      return NB_ERR_ARG;
-    }
+    if (!po_check_bin(j, k, e, b)) return NB_ERR_ARG;
     host[j] = k;
     host[p + j] = k > 0.0 ? 1.0 / k : 0.0;
     host[2 * p + j] = e;
@@ -1578,6 +1585,111 @@ int nb_poisson_loglike(const nb_poisson* h, const double* model, int64_t ld,
   }
   return nb_launch_poisson(h->dev, h->n_data, model, ld, n, h->log_const, out,
                            as_stream(stream));
+}
+
+// The table of nb_poisson and the response matrix packed for nb_fold.hip
+// (nb_common.h, nb_fold_r_offset), uploaded once.
+struct nb_fold_poisson {
+  double* dev = nullptr;
+  int n_data = 0;
+  int n_src = 0;
+  double log_const = 0.0;
+};
+
+int nb_fold_poisson_create(int32_t n_data, int32_t n_src, const double* counts,
+                           const double* response, int64_t ld_response,
+                           const double* exposure, const double* background,
+                           double log_const, nb_fold_poisson** out) {
+  // the sizes before any array is read
+  const bool sizes = n_data >= 1 && n_data <= NB_POISSON_MAX_DATA &&
+                     n_src >= 1 && n_src <= NB_FOLD_MAX_SOURCE &&
+                     ((int64_t)(n_data + 15) / 16) * ((n_src + 15) / 16) * 256 <=
+                         NB_FOLD_MAX_RESPONSE;
+  if (out == nullptr || counts == nullptr || response == nullptr || !sizes ||
+      ld_response < n_src || !std::isfinite(log_const)) {
+    nb_set_error("bad folded Poisson likelihood arguments (n_data 1..%d, "
+                 "n_src 1..%d, ceil16(n_data) ceil16(n_src) <= %d, counts, "
+                 "response with ld_response >= n_src, a finite log_const)",
+                 NB_POISSON_MAX_DATA, NB_FOLD_MAX_SOURCE,
+                 NB_FOLD_MAX_RESPONSE);
+    return NB_ERR_ARG;
+  }
+  *out = nullptr;
+  const size_t p = (size_t)n_data, ks = (size_t)n_src;
+  const int dt = (n_data + 15) / 16, nkt = (n_src + 15) / 16;
+  const size_t pp = 16 * (size_t)dt;             // padded table arrays
+  std::vector<double> host(nb_fold_r_offset(dt) +
+                               (size_t)dt * (size_t)nkt * NB_TILE, 0.0);
+  for (size_t j = 0; j < pp; ++j) host[2 * pp + j] = 1.0;
+  for (size_t j = 0; j < p; ++j) {
+    const double k = counts[j];
+    const double e = exposure != nullptr ? exposure[j] : 1.0;
+    const double b = background != nullptr ? background[j] : 0.0;
+    if (!po_check_bin(j, k, e, b)) return NB_ERR_ARG;
+    host[j] = k;
+    host[pp + j] = k > 0.0 ? 1.0 / k : 0.0;
+    host[2 * pp + j] = e;
+    host[3 * pp + j] = b;
+    for (size_t c = 0; c < ks; ++c)
+      if (!std::isfinite(response[j * (size_t)ld_response + c])) {
+        nb_set_error("response entry (%zu, %zu) is not finite", j, c);
+        return NB_ERR_ARG;
+      }
+  }
+  // operand tiles: lane group lg of k-step s holds column 4 lg + s of the
+  // k-tile (what a staging thread of the kernel reads as 32 contiguous bytes
+  // of a source row)
+  double* tile = host.data() + nb_fold_r_offset(dt);
+  const int n_panels = (dt + NB_FOLD_PANEL - 1) / NB_FOLD_PANEL;
+  for (int pn = 0; pn < n_panels; ++pn) {
+    const int nrt = std::min(NB_FOLD_PANEL, dt - NB_FOLD_PANEL * pn);
+    for (int kt = 0; kt < nkt; ++kt)
+      for (int ti = 0; ti < nrt; ++ti, tile += NB_TILE)
+        for (int l = 0; l < 16; ++l) {
+          const size_t h = 16 * (size_t)(NB_FOLD_PANEL * pn + ti) + l;
+          if (h >= p) break;
+          const double* row = response + h * (size_t)ld_response;
+          for (int c = 0; c < 16; ++c) {
+            const size_t k = 16 * (size_t)kt + c;
+            if (k < ks) tile[(c & 3) * 64 + (c >> 2) * 16 + l] = row[k];
+          }
+        }
+  }
+  nb_fold_poisson* f = new nb_fold_poisson;
+  f->n_data = n_data;
+  f->n_src = n_src;
+  f->log_const = log_const;
+  const size_t bytes = host.size() * sizeof(double);
+  hipError_t e = hipMalloc((void**)&f->dev, bytes);
+  if (e == hipSuccess)
+    e = hipMemcpy(f->dev, host.data(), bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    nb_set_error("folded Poisson likelihood upload failed: %s",
+                 hipGetErrorString(e));
+    if (f->dev != nullptr) (void)hipFree(f->dev);
+    delete f;
+    return NB_ERR_HIP;
+  }
+  *out = f;
+  return NB_OK;
+}
+
+int nb_fold_poisson_destroy(nb_fold_poisson* h) {
+  if (h == nullptr) return NB_OK;
+  (void)hipFree(h->dev);
+  delete h;
+  return NB_OK;
+}
+
+int nb_fold_poisson_loglike(const nb_fold_poisson* h, const double* src,
+                            int64_t ld, int64_t n, double* out, void* stream) {
+  if (h == nullptr || n < 0 || (n > 1 && ld < h->n_src) ||
+      (n > 0 && (src == nullptr || out == nullptr))) {
+    nb_set_error("bad folded Poisson likelihood arguments (ld >= n_src)");
+    return NB_ERR_ARG;
+  }
+  return nb_launch_fold_poisson(h->dev, h->n_data, h->n_src, src, ld, n,
+                                h->log_const, out, as_stream(stream));
 }
 
 int nb_live_append(const double* log_l, int64_t n, const double* thr,

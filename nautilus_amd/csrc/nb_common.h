@@ -133,6 +133,19 @@ int nb_launch_poisson(const double* tab, int n_data, const double* model,
                       long long ld, long long n, double log_const,
                       double* out, hipStream_t stream);
 
+// Poisson likelihood behind a response matrix (nb_fold.hip).  The blob is the
+// table above with each array zero padded to 16 DT doubles (1 for the
+// exposure), then R (P x K) as 16x16 operand tiles, zero padded, in the order
+// the kernel walks them: panels of NB_FOLD_PANEL row tiles; per panel every
+// k-tile; per k-tile the panel's row tiles.
+#define NB_FOLD_PANEL 16
+__host__ __device__ constexpr size_t nb_fold_r_offset(int dt) {
+  return 64 * (size_t)dt;
+}
+int nb_launch_fold_poisson(const double* blob, int n_data, int n_src,
+                           const double* src, long long ld, long long n,
+                           double log_const, double* out, hipStream_t stream);
+
 // One (bound, neural bound) group of a two-stage query (nb_cand.hip ->
 // nb_eval_fast.hip, BATCH): built on the host when a bound / a bound list is
 // created, read by the second stage per 128-point pass.

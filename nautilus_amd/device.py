@@ -719,6 +719,61 @@ class PoissonTable:
         return out
 
 
+class FoldedPoissonTable:
+    """Device-resident bins and response matrix of a Poisson likelihood whose
+    model lives in a source space (``nb_fold_poisson_create``): ``counts``,
+    ``exposure``, ``background`` and ``log_const`` as in ``PoissonTable``,
+    ``response`` (P, K) finite, mapping K source values onto the P bins.
+    Packed and uploaded once; every ``loglike`` is one launch on the current
+    stream that never stores the (n, P) expected counts."""
+
+    def __init__(self, counts, response, exposure=None, background=None,
+                 log_const=0.0):
+        self._lib = lib = _lib.load()
+        counts = _f64(counts)
+        if counts.ndim != 1:
+            raise ValueError('counts must be one-dimensional')
+        self.n_data = p = len(counts)
+        response = _f64(response)
+        if response.ndim != 2 or response.shape[0] != p:
+            raise ValueError('response must have shape (%d, K)' % p)
+        self.n_source = k = response.shape[1]
+        if exposure is not None:
+            exposure = _f64(exposure)
+            if exposure.shape != (p,):
+                raise ValueError('exposure must have shape (%d,)' % p)
+        if background is not None:
+            background = _f64(background)
+            if background.shape != (p,):
+                raise ValueError('background must have shape (%d,)' % p)
+        h = C.c_void_p()
+        _lib.check(lib.nb_fold_poisson_create(
+            p, k, _dp(counts), _dp(response), k,
+            None if exposure is None else _dp(exposure),
+            None if background is None else _dp(background),
+            float(log_const), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, '_h', None)
+        if h:
+            self._lib.nb_fold_poisson_destroy(h)
+            self._h = None
+
+    def loglike(self, src, ld=None):
+        """log L of the rows of the cuda float64 tensor ``src`` (n, K), read
+        in place: its rows may be strided (``stride(1) == 1``,
+        ``stride(0) >= K``).  ``ld`` overrides the row stride (in doubles)
+        the tensor reports."""
+        n = src.shape[0]
+        if ld is None:
+            ld = src.stride(0) if n > 1 else self.n_source
+        out = torch.empty(n, dtype=torch.float64, device=src.device)
+        _lib.check(self._lib.nb_fold_poisson_loglike(
+            self._h, _ptr(src), ld, n, _ptr(out), _stream()))
+        return out
+
+
 
 def gmm_fit(x, n_init=10, seed=0, tol=1e-3, reg_covar=1e-6, max_iter=100,
             init_labels=None):

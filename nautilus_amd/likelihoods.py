@@ -346,6 +346,8 @@ class GaussianDataLikelihood:
 
 
 N_COUNTS_MAX = 1 << 20             # NB_POISSON_MAX_DATA of nautilus_hip.h
+N_SOURCE_MAX = 1 << 20             # NB_FOLD_MAX_SOURCE
+N_RESPONSE_MAX = 1 << 24           # NB_FOLD_MAX_RESPONSE, doubles when packed
 
 
 def poisson_log_const(counts):
@@ -426,12 +428,23 @@ class PoissonDataLikelihood:
 
     In row i,  mu = 0 in a bin with k > 0 makes ``out[i]`` -inf (mu = 0 with
     k = 0 contributes 0); a negative, NaN or infinite mu makes it NaN, also
-    next to a -inf bin.  Neither changes a bit of any other row."""
+    next to a -inf bin.  Neither changes a bit of any other row.
+
+    With ``response`` = a (P, K) matrix R the model lives in a source space:
+    it returns (n, K) values s (fluxes in K true-energy bins, amplitudes of K
+    templates) and  mu_j = exposure_j sum_k R_jk s_k + background_j.  R may
+    hold any finite values; ceil16(P) ceil16(K) is at most 2^24 (4096 x 4096,
+    or 2^20 x 16).  The fused kernel ``nb_fold_poisson_loglike`` forms the mu
+    on the fp64 matrix cores and feeds them straight into the deviance, so
+    the (n, P) expected counts are never stored; ``from_model`` then takes
+    (n, K) under the same layout rules, ``n_source`` is K, and the numpy
+    twins fold with ``s @ R.T`` first.  A NaN or infinite source value makes
+    its row NaN, also where the column of R it meets is all zeros."""
 
     device = True
 
     def __init__(self, model, counts, *, exposure=None, background=None,
-                 normalised=True):
+                 normalised=True, response=None):
         if not callable(model):
             raise ValueError('model must be callable')
         self.model = model
@@ -469,6 +482,27 @@ class PoissonDataLikelihood:
                 raise ValueError('background must be %d finite numbers that '
                                  'are not negative' % p)
             self.background = background.copy()
+        if response is None:
+            self.response = None
+            self.n_source = p
+        else:
+            response = np.asarray(response, float)
+            if response.ndim != 2 or response.shape[0] != p or \
+                    response.shape[1] < 1:
+                raise ValueError('response must have shape (%d, K) with K >= '
+                                 '1, not %s' % (p, response.shape))
+            k_src = response.shape[1]
+            if k_src > N_SOURCE_MAX or \
+                    16 * ((p + 15) // 16) * 16 * ((k_src + 15) // 16) > \
+                    N_RESPONSE_MAX:
+                raise ValueError(
+                    'the response is too large: K <= %d and ceil16(P) '
+                    'ceil16(K) <= %d are supported, not %s' %
+                    (N_SOURCE_MAX, N_RESPONSE_MAX, response.shape))
+            if not np.all(np.isfinite(response)):
+                raise ValueError('response must be finite')
+            self.response = response.copy()
+            self.n_source = k_src
         # 1 / k as the device table holds it: 0 where k = 0
         self._inv_counts = np.zeros(p)
         np.divide(1.0, counts, out=self._inv_counts, where=counts > 0)
@@ -482,26 +516,32 @@ class PoissonDataLikelihood:
         """The device handle of the current device, built on first use."""
         dev = torch.cuda.current_device()
         if dev not in self._tables:
-            self._tables[dev] = device.PoissonTable(
-                self.counts, self.exposure, self.background,
-                log_const=self.log_const)
+            if self.response is None:
+                self._tables[dev] = device.PoissonTable(
+                    self.counts, self.exposure, self.background,
+                    log_const=self.log_const)
+            else:
+                self._tables[dev] = device.FoldedPoissonTable(
+                    self.counts, self.response, self.exposure,
+                    self.background, log_const=self.log_const)
         return self._tables[dev]
 
     def _check(self, m):
-        if m.ndim != 2 or m.shape[1] != self.n_data:
+        if m.ndim != 2 or m.shape[1] != self.n_source:
             raise ValueError('the model output must have shape (n, %d), not '
-                             '%s' % (self.n_data, tuple(m.shape)))
+                             '%s' % (self.n_source, tuple(m.shape)))
 
     def from_model(self, m):
-        """log L of the rows of an (n, P) float64 model output: a cuda tensor
-        in, a cuda tensor out; numpy in, numpy out."""
+        """log L of the rows of an (n, P) float64 model output ((n, K) with a
+        response): a cuda tensor in, a cuda tensor out; numpy in, numpy
+        out."""
         if isinstance(m, torch.Tensor):
             if m.dtype != torch.float64:
                 raise ValueError('the model output must be float64, not %s' %
                                  m.dtype)
             self._check(m)
             t = m if m.is_cuda else m.cuda()
-            p = self.n_data
+            p = self.n_source
             in_place = (p == 1 or t.stride(1) == 1) and \
                 (t.shape[0] <= 1 or t.stride(0) >= p)
             return self._table().loglike(t if in_place else t.contiguous())
@@ -520,13 +560,16 @@ class PoissonDataLikelihood:
         return self.from_model(self.model(xs)).cpu().numpy()
 
     def numpy_deviance(self, m):
-        """The (n, P) terms D(mu_ij, k_j) of an (n, P) model output in pure
-        numpy, by the formulas of the class docstring: +inf where mu = 0 and
-        k > 0, NaN where mu is negative, NaN or infinite."""
+        """The (n, P) terms D(mu_ij, k_j) of an (n, P) model output ((n, K)
+        with a response) in pure numpy, by the formulas of the class
+        docstring: +inf where mu = 0 and k > 0, NaN where mu is negative, NaN
+        or infinite."""
         m = np.asarray(m, float)
         self._check(m)
         k, ik = self.counts, self._inv_counts
         with np.errstate(all='ignore'):
+            if self.response is not None:
+                m = m @ self.response.T
             mu = self.exposure * m + self.background
             fin = (mu >= 0) & (mu < np.inf)
             pos = np.broadcast_to(k > 0, mu.shape)
@@ -541,8 +584,8 @@ class PoissonDataLikelihood:
         return d
 
     def numpy_from_model(self, m):
-        """Pure-numpy evaluation of an (n, P) model output (CPU baseline /
-        oracle runs / tests)."""
+        """Pure-numpy evaluation of an (n, P) model output, (n, K) with a
+        response (CPU baseline / oracle runs / tests)."""
         d = self.numpy_deviance(m)
         flagged = ~np.isfinite(d)
         out = self.log_const - np.sum(np.where(flagged, 0.0, d), axis=1)
