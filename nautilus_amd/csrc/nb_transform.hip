@@ -36,32 +36,54 @@ nb_transform_kernel(const double* __restrict__ blk, int n_dim,
 }
 
 // per-column mean and population standard deviation (two passes, fixed
-// reduction order), one workgroup per column
+// reduction order), one workgroup per column.  The first pass gives the mean
+// to the rounding of a sum of n terms, a few ulp OF THE MEAN.  In a column
+// that lies far from zero (mean 1e6, spread 1) that is 1e-10 of the spread,
+// and nb_standardize_kernel puts it into every coordinate of the column.  So
+// the second pass also sums the residuals x - centre, which are small and
+// exact, and where their mean exceeds NB_MEAN_SHIFT standard deviations the
+// mean is centre plus that shift: correctly rounded but for ties.  Below the
+// threshold the standardised points move by less than their own rounding and
+// the first-pass mean stands, so columns centred near zero (the unit cube,
+// ellipsoid-frame coordinates) keep the values they always had.  The
+// deviation is the one about `centre` in either case: the two differ by the
+// square of the shift, below its rounding.
+constexpr double NB_MEAN_SHIFT = 1e-12;
+
 __global__ void __launch_bounds__(256)
 nb_colstats_kernel(const double* __restrict__ x, long long n, int d,
                    double* __restrict__ mean, double* __restrict__ scale) {
-  __shared__ double red[4];
+  __shared__ double red[2][4];
   const int col = blockIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double result[2];
-  double centre = 0.0;
+  double centre = 0.0, shift = 0.0;
   for (int pass = 0; pass < 2; ++pass) {
-    double s = 0.0;
+    double s = 0.0, r = 0.0;
     for (long long i = threadIdx.x; i < n; i += 256) {
       const double v = x[i * d + col] - centre;
       s += pass == 0 ? v : v * v;
+      r += v;
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    for (int o = 32; o > 0; o >>= 1) {
+      s += __shfl_xor(s, o);
+      r += __shfl_xor(r, o);
+    }
     __syncthreads();
-    if (lane == 0) red[wave] = s;
+    if (lane == 0) {
+      red[0][wave] = s;
+      red[1][wave] = r;
+    }
     __syncthreads();
-    result[pass] = (red[0] + red[1] + red[2] + red[3]) / (double)n;
+    result[pass] = (red[0][0] + red[0][1] + red[0][2] + red[0][3]) / (double)n;
     if (pass == 0) centre = result[0];
+    else shift = (red[1][0] + red[1][1] + red[1][2] + red[1][3]) / (double)n;
   }
   if (threadIdx.x == 0) {
-    mean[col] = result[0];
-    scale[col] = sqrt(result[1]);
+    const double sd = sqrt(result[1]);
+    mean[col] = fabs(shift) > NB_MEAN_SHIFT * sd ? centre + shift : centre;
+    scale[col] = sd;
   }
 }
 

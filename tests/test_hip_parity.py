@@ -838,13 +838,9 @@ def _sklearn_em_from_labels(x, labels, **kw):
         return gmm.fit(x)
 
 
-@pytest.mark.parametrize('d,n', [(2, 300), (7, 500), (20, 1500), (50, 2000),
-                                 (63, 700), (64, 900), (100, 3000),
-                                 (127, 1200), (128, 1000)])
-def test_gmm_em_matches_sklearn(dev, d, n):
-    """nb_gmm_fit against scikit-learn 1.7 (the reference's dependency for
-    Union.split, union.py:185-187): same initial assignment -> same EM
-    trajectory (number of iterations, lower bound, parameters)."""
+def _gmm_two_clouds(d, n):
+    """Two Gaussian clouds three units apart along the first axis, and three
+    initial assignments: the right cut, a wrong one, a random one."""
     rng = np.random.default_rng(d)
     shift = np.zeros(d)
     shift[0] = 3.0
@@ -854,7 +850,10 @@ def test_gmm_em_matches_sklearn(dev, d, n):
     inits = np.array([(x[:, 0] > 1.5).astype(np.int32),
                       (x[:, 1] > 0.0).astype(np.int32),
                       rng.integers(0, 2, n).astype(np.int32)])
-    fits = dev.gmm_fit(x, n_init=3, init_labels=inits)
+    return x, inits
+
+
+def _check_gmm_against_sklearn(x, inits, fits):
     for lab, fit in zip(inits, fits):
         ref = _sklearn_em_from_labels(x, lab)
         assert not fit['failed']
@@ -865,6 +864,44 @@ def test_gmm_em_matches_sklearn(dev, d, n):
         assert np.allclose(fit['means'], ref.means_, rtol=0, atol=1e-8)
         assert np.allclose(fit['covariances'], ref.covariances_, rtol=0,
                            atol=1e-8)
+
+
+# (n_dim 15..112 of the second row: the first and the last n_dim of the tile
+# counts ceil((n_dim + 1) / 16) = 1..7 and an odd one inside counts 3 and 6,
+# tests/test_tile_counts_gpu.py; n = 8 n_dim + 203, ragged in every tiling)
+@pytest.mark.parametrize('d,n', [(2, 300), (7, 500), (20, 1500), (50, 2000),
+                                 (63, 700), (64, 900), (100, 3000),
+                                 (127, 1200), (128, 1000)] +
+                         [(d, 8 * d + 203) for d in (
+                             15, 16, 31, 32, 39, 47, 48, 79, 80, 87, 95, 96,
+                             111, 112)])
+def test_gmm_em_matches_sklearn(dev, d, n):
+    """nb_gmm_fit against scikit-learn 1.7 (the reference's dependency for
+    Union.split, union.py:185-187): same initial assignment -> same EM
+    trajectory (number of iterations, lower bound, parameters)."""
+    x, inits = _gmm_two_clouds(d, n)
+    _check_gmm_against_sklearn(x, inits,
+                               dev.gmm_fit(x, n_init=3, init_labels=inits))
+
+
+@pytest.mark.parametrize('d', [39, 87])
+def test_gmm_one_workgroup_per_restart(dev, d):
+    """``nb_gmm_set_max_wgs(1)``, what parallel.py switches on for ranks that
+    share a device: the 3000 points of a restart go through ONE workgroup
+    instead of eleven.  Same trajectory as scikit-learn's and as the uncapped
+    fit's."""
+    from nautilus_amd import _lib
+    x, inits = _gmm_two_clouds(d, 3000)
+    free = dev.gmm_fit(x, n_init=3, init_labels=inits)
+    lib = _lib.load()
+    try:
+        _lib.check(lib.nb_gmm_set_max_wgs(1))
+        capped = dev.gmm_fit(x, n_init=3, init_labels=inits)
+    finally:
+        _lib.check(lib.nb_gmm_set_max_wgs(0))
+    _check_gmm_against_sklearn(x, inits, capped)
+    for a, b in zip(capped, free):
+        assert a['n_iter'] == b['n_iter'] and a['converged'] == b['converged']
 
 
 def test_gmm_full_fit(dev):
@@ -1307,11 +1344,14 @@ def test_emulator_training_ragged_batches(dev):
         assert np.allclose(nets[0].coefs_[0], ref.coefs[0], rtol=0, atol=1e-8)
 
 
-@pytest.mark.parametrize('d', [63, 64, 65, 80, 100, 112, 127, 128])
+@pytest.mark.parametrize('d', [15, 16, 31, 32, 39, 46, 47, 48, 63, 64, 65,
+                               79, 80, 95, 96, 100, 111, 112, 127, 128])
 def test_emulator_training_wide_inputs(dev, d):
-    """The trainer beyond 64 input dimensions (five to nine k-tiles in layer
-    1: other register schedules, a different job list of the gradient phase)
-    against the restated MLPRegressor.fit -- configuration 5 trains at 100."""
+    """The trainer from 15 to 128 input dimensions: the last n_dim of one
+    k-tile in layer 1, both ends of two to eight k-tiles, nine at 128 (other
+    register schedules, a different job list of the gradient phase per
+    count), and 39 and 46 inside the three k-tiles of n_dim 32..47 -- against
+    the restated MLPRegressor.fit; configuration 5 trains at 100."""
     import torch
     from nautilus_amd import emulator
     from oracle import mlp_oracle as mo
