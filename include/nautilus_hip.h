@@ -548,6 +548,50 @@ int nb_fold_poisson_loglike(const nb_fold_poisson* h, const double* src_dev,
                             void* stream);
 int nb_fold_poisson_destroy(nb_fold_poisson* h);
 
+/* Gaussian likelihood of P measurements d whose variance depends on the point
+ * (the user-side callable of sampler.py:863-873 for a model prediction
+ * m(theta) under error bars with free parameters: an inflation factor, a
+ * jitter added in quadrature, a fractional model error), one streaming launch
+ * that reads every model row once:
+ *   out_dev[i] = log_norm - 1/2 sum_j [ (m_ij - d_j)^2 / v_ij + log v_ij ],
+ *   mode NB_NOISE_ROW:   v_ij = c_i sigma2_j + a_i + f_i m_ij^2, row i of the
+ *                        noise holding the three doubles (c_i, a_i, f_i);
+ *   mode NB_NOISE_FULL:  v_ij = sigma2_j + w_ij, row i of the noise holding
+ *                        n_data doubles w_ij.
+ * The log v term always stays; with log_norm = -(P/2) log 2 pi the result is
+ * sum_j log N(d_j | m_ij, v_ij).  No log is taken per element: the mantissas
+ * of the v are multiplied, their exponents added, and a lane takes one log
+ * per product at the end of its row.
+ * data [P] finite; sigma2 [P] = sigma^2, finite and >= 0 (zero is legal: the
+ * noise may carry the whole variance), or NULL (= 0): host arrays, read here
+ * and uploaded once.  NB_ERR_ARG: n_data outside 1..NB_NOISE_MAX_DATA, NULL or
+ * non-finite data, a negative or non-finite sigma2, a non-finite log_norm.
+ * nb_noise_loglike (sampler.py:863-873) only launches, on the caller's stream
+ * (one handle serves any number of streams): row i of the model is the n_data
+ * doubles at model_dev + i * ld, row i of the noise the 3 or n_data doubles at
+ * noise_dev + i * ld_noise (NB_ERR_ARG for an unknown mode, for ld < n_data or
+ * ld_noise < 3 resp. n_data with n > 1, and for a NULL pointer with n > 0).
+ * A row with an m_ij that is not finite, or a v_ij that is not in (0, +inf) --
+ * zero, negative, NaN or infinite, whatever coefficient caused it -- is NaN
+ * and changes no other row; the signs of the single coefficients do not
+ * matter as long as v > 0.  The bits of a row depend on neither n, its
+ * position in the batch, ld, ld_noise, the stream nor the grid.  n = 0
+ * returns NB_OK without a launch.  ((m - d)^2 / v must stay below the float64
+ * maximum, and v at or above 2^-1022 for 1 / v to be finite: what a row
+ * beyond either gives is not specified.)
+ *  nb_noise_destroy frees the handle of the same callable
+ * (sampler.py:863-873); NULL is NB_OK.                                      */
+typedef struct nb_noise nb_noise;
+#define NB_NOISE_MAX_DATA (1 << 20)
+#define NB_NOISE_ROW 0
+#define NB_NOISE_FULL 1
+int nb_noise_create(int32_t n_data, const double* data, const double* sigma2,
+                    double log_norm, nb_noise** out);
+int nb_noise_loglike(const nb_noise* h, int32_t mode, const double* model_dev,
+                     int64_t ld, const double* noise_dev, int64_t ld_noise,
+                     int64_t n, double* out_dev, void* stream);
+int nb_noise_destroy(nb_noise* h);
+
 
 /* Two-stage evaluation of bounds with several outer members, several neural
  * bounds, or of lists of bounds (bounds/union.py:285-289, 316-319;

@@ -19,6 +19,7 @@ _LAZY = {
     'GaussianMixtureLikelihood': 'likelihoods', 'unit_prior': 'likelihoods',
     'GaussianDataLikelihood': 'likelihoods',
     'PoissonDataLikelihood': 'likelihoods',
+    'GaussianNoiseLikelihood': 'likelihoods',
     'RosenbrockLikelihood': 'likelihoods', 'FunnelLikelihood': 'likelihoods',
 }
 

@@ -1692,6 +1692,81 @@ int nb_fold_poisson_loglike(const nb_fold_poisson* h, const double* src,
                                 h->log_const, out, as_stream(stream));
 }
 
+// Data and sigma^2 for nb_noise.hip, uploaded once.
+struct nb_noise {
+  double* dev = nullptr;
+  int n_data = 0;
+  double log_norm = 0.0;
+};
+
+int nb_noise_create(int32_t n_data, const double* data, const double* sigma2,
+                    double log_norm, nb_noise** out) {
+  if (out == nullptr || data == nullptr || n_data < 1 ||
+      n_data > NB_NOISE_MAX_DATA || !std::isfinite(log_norm)) {
+    nb_set_error("bad noise likelihood arguments (n_data 1..%d, data, a "
+                 "finite log_norm)", NB_NOISE_MAX_DATA);
+    return NB_ERR_ARG;
+  }
+  *out = nullptr;
+  const size_t p = (size_t)n_data;
+  std::vector<double> host(2 * p, 0.0);
+  for (size_t j = 0; j < p; ++j) {
+    if (!std::isfinite(data[j])) {
+      nb_set_error("data point %zu must be finite", j);
+      return NB_ERR_ARG;
+    }
+    host[j] = data[j];
+    if (sigma2 == nullptr) continue;
+    if (!std::isfinite(sigma2[j]) || sigma2[j] < 0.0) {
+      nb_set_error("sigma2 %zu must be finite and not negative", j);
+      return NB_ERR_ARG;
+    }
+    host[p + j] = sigma2[j];
+  }
+  nb_noise* c = new nb_noise;
+  c->n_data = n_data;
+  c->log_norm = log_norm;
+  const size_t bytes = host.size() * sizeof(double);
+  hipError_t e = hipMalloc((void**)&c->dev, bytes);
+  if (e == hipSuccess)
+    e = hipMemcpy(c->dev, host.data(), bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    nb_set_error("noise likelihood upload failed: %s", hipGetErrorString(e));
+    if (c->dev != nullptr) (void)hipFree(c->dev);
+    delete c;
+    return NB_ERR_HIP;
+  }
+  *out = c;
+  return NB_OK;
+}
+
+int nb_noise_destroy(nb_noise* h) {
+  if (h == nullptr) return NB_OK;
+  (void)hipFree(h->dev);
+  delete h;
+  return NB_OK;
+}
+
+int nb_noise_loglike(const nb_noise* h, int32_t mode, const double* model,
+                     int64_t ld, const double* noise, int64_t ld_noise,
+                     int64_t n, double* out, void* stream) {
+  if (h == nullptr || n < 0 ||
+      (mode != NB_NOISE_ROW && mode != NB_NOISE_FULL)) {
+    nb_set_error("bad noise likelihood arguments (a handle, n >= 0, mode "
+                 "NB_NOISE_ROW or NB_NOISE_FULL)");
+    return NB_ERR_ARG;
+  }
+  const int64_t width = mode == NB_NOISE_ROW ? 3 : h->n_data;
+  if ((n > 1 && (ld < h->n_data || ld_noise < width)) ||
+      (n > 0 && (model == nullptr || noise == nullptr || out == nullptr))) {
+    nb_set_error("bad noise likelihood arguments (ld >= n_data, ld_noise >= "
+                 "%lld, no NULL pointer)", (long long)width);
+    return NB_ERR_ARG;
+  }
+  return nb_launch_noise(h->dev, h->n_data, mode, model, ld, noise, ld_noise,
+                         n, h->log_norm, out, as_stream(stream));
+}
+
 int nb_live_append(const double* log_l, int64_t n, const double* thr,
                    double* pool, int32_t* pool_n, int32_t capacity,
                    int32_t* overflow, void* stream) {

@@ -133,6 +133,14 @@ int nb_launch_poisson(const double* tab, int n_data, const double* model,
                       long long ld, long long n, double log_const,
                       double* out, hipStream_t stream);
 
+// Gaussian likelihood with a variance that depends on the point
+// (nb_noise.hip).  The table is two arrays of P doubles: d, sigma^2.  mode is
+// NB_NOISE_ROW (noise: n rows of c, a, f) or NB_NOISE_FULL (n rows of P).
+int nb_launch_noise(const double* tab, int n_data, int mode,
+                    const double* model, long long ld, const double* noise,
+                    long long ld_noise, long long n, double log_norm,
+                    double* out, hipStream_t stream);
+
 // Poisson likelihood behind a response matrix (nb_fold.hip).  The blob is the
 // table above with each array zero padded to 16 DT doubles (1 for the
 // exposure), then R (P x K) as 16x16 operand tiles, zero padded, in the order

@@ -774,6 +774,70 @@ class FoldedPoissonTable:
         return out
 
 
+NOISE_ROW, NOISE_FULL = 0, 1       # NB_NOISE_ROW, NB_NOISE_FULL
+
+
+def noise_launch_shape(n_data):
+    """(L, R, U) of ``nb_noise_loglike`` at P = ``n_data`` (nb_noise.hip,
+    ``launch_mode``): L lanes share a row, R rows and U column blocks per
+    step.  A row's partial sums pass through ceil(P / (L U)) + log2(L U)
+    additions."""
+    if n_data <= 32:
+        return 16, 4, 1
+    if n_data <= 512:
+        return 16, 2, 2
+    return 64, 1, 4
+
+
+class NoiseTable:
+    """Device-resident measurements of a Gaussian likelihood whose variance
+    depends on the point (``nb_noise_create``): ``data`` (P,) finite and
+    ``sigma2`` (P,) = sigma^2 >= 0 (None = 0), with ``log_norm`` added to
+    every result.  Uploaded once; every ``loglike`` is one launch on the
+    current stream."""
+
+    def __init__(self, data, sigma2=None, log_norm=0.0):
+        self._lib = lib = _lib.load()
+        data = _f64(data)
+        if data.ndim != 1:
+            raise ValueError('data must be one-dimensional')
+        self.n_data = p = len(data)
+        if sigma2 is not None:
+            sigma2 = _f64(sigma2)
+            if sigma2.shape != (p,):
+                raise ValueError('sigma2 must have shape (%d,)' % p)
+        h = C.c_void_p()
+        _lib.check(lib.nb_noise_create(
+            p, _dp(data), None if sigma2 is None else _dp(sigma2),
+            float(log_norm), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, '_h', None)
+        if h:
+            self._lib.nb_noise_destroy(h)
+            self._h = None
+
+    def loglike(self, model, noise, mode, ld=None, ld_noise=None):
+        """log L of the rows of the cuda float64 tensors ``model`` (n, P) and
+        ``noise`` ((n, 3) with ``mode`` NOISE_ROW, (n, P) with NOISE_FULL),
+        both read in place: their rows may be strided (``stride(1) == 1``,
+        ``stride(0)`` at least the width).  ``ld`` and ``ld_noise`` override
+        the row strides (in doubles) the tensors report."""
+        n = model.shape[0]
+        if noise.shape[0] != n:
+            raise ValueError('model and noise must have the same number of '
+                             'rows, not %d and %d' % (n, noise.shape[0]))
+        if ld is None:
+            ld = model.stride(0) if n > 1 else self.n_data
+        if ld_noise is None:
+            ld_noise = noise.stride(0) if n > 1 else noise.shape[1]
+        out = torch.empty(n, dtype=torch.float64, device=model.device)
+        _lib.check(self._lib.nb_noise_loglike(
+            self._h, mode, _ptr(model), ld, _ptr(noise), ld_noise, n,
+            _ptr(out), _stream()))
+        return out
+
 
 def gmm_fit(x, n_init=10, seed=0, tol=1e-3, reg_covar=1e-6, max_iter=100,
             init_labels=None):

@@ -607,6 +607,197 @@ class PoissonDataLikelihood:
         return state
 
 
+N_NOISE_MAX = 1 << 20              # NB_NOISE_MAX_DATA of nautilus_hip.h
+
+
+class GaussianNoiseLikelihood:
+    """Gaussian likelihood of independent measurements whose error bars carry
+    free parameters:
+
+        log L(theta) = log_norm - 1/2 sum_j [ (m_j - d_j)^2 / v_j + log v_j ].
+
+    The variance v depends on the point, so the ``log v`` term always stays;
+    ``log_norm = -(P/2) log 2 pi``, or 0 with ``normalised=False``.
+
+    ``data`` holds the P finite measurements, P at most 2^20; ``sigma`` the P
+    quoted error bars, finite and >= 0 (``None`` = all zero; zero is legal
+    because the model noise may carry the whole variance).  ``model`` takes
+    the (n, n_dim) batch of points as a torch tensor and returns a pair
+    ``(m, w)`` of float64 tensors on the same device: ``m`` the (n, P)
+    predictions and ``w`` the noise,
+
+      noise='row'   w is (n, 3) with columns (c, a, f):
+                    v_ij = c_i sigma_j^2 + a_i + f_i m_ij^2 -- an error
+                    inflation factor, a jitter variance added in quadrature
+                    and a fractional model variance, one triple per point;
+      noise='full'  w is (n, P):  v_ij = sigma_j^2 + w_ij, any variance model.
+
+    A call evaluates the model and then runs the fused kernel
+    ``nb_noise_loglike`` -- one streaming launch on the current stream that
+    reads every row once and takes no log per element (the mantissas of the v
+    are multiplied and their exponents added).  ``from_model`` is the second
+    half alone; it reads a cuda tensor whose rows are strided
+    (``stride(1) == 1``, ``stride(0)`` at least the width, such as a column
+    slice of a wider tensor) in place and copies anything else to contiguous,
+    separately for ``m`` and ``w``.  ``numpy`` / ``numpy_from_model`` are the
+    pure-numpy twins, ``numpy_terms`` the two matrices of the summands.
+
+    Row i is NaN when any m_ij is not finite or any v_ij is not in (0, +inf):
+    zero, negative, NaN or infinite, whichever coefficient caused it.  That
+    changes no bit of any other row.  The signs of the single coefficients do
+    not matter as long as v > 0."""
+
+    device = True
+
+    def __init__(self, model, data, sigma=None, *, noise='row',
+                 normalised=True):
+        if not callable(model):
+            raise ValueError('model must be callable')
+        self.model = model
+        if noise not in ('row', 'full'):
+            raise ValueError("noise must be 'row' or 'full', not %r" %
+                             (noise,))
+        self.noise = noise
+        data = np.asarray(data, float)
+        if data.ndim != 1 or len(data) < 1:
+            raise ValueError('data must be a vector of at least one number')
+        if len(data) > N_NOISE_MAX:
+            raise ValueError('at most %d data points are supported, not %d' %
+                             (N_NOISE_MAX, len(data)))
+        if not np.all(np.isfinite(data)):
+            raise ValueError('data must be finite')
+        self.data = data.copy()
+        self.n_data = p = len(data)
+        if sigma is None:
+            self.sigma = np.zeros(p)
+        else:
+            sigma = np.asarray(sigma, float)
+            if sigma.shape != (p,) or not np.all(np.isfinite(sigma)) or \
+                    not np.all(sigma >= 0):
+                raise ValueError('sigma must be %d finite numbers that are '
+                                 'not negative' % p)
+            self.sigma = sigma.copy()
+        with np.errstate(over='ignore'):
+            self._sigma2 = self.sigma * self.sigma
+        if not np.all(np.isfinite(self._sigma2)):
+            raise ValueError('sigma is too large: sigma^2 is not finite')
+        self.log_norm = -0.5 * p * np.log(2 * np.pi) if normalised else 0.0
+        self._tables = {}
+
+    @property
+    def _width(self):
+        return 3 if self.noise == 'row' else self.n_data
+
+    def _table(self):
+        """The device handle of the current device, built on first use."""
+        dev = torch.cuda.current_device()
+        if dev not in self._tables:
+            self._tables[dev] = device.NoiseTable(
+                self.data, self._sigma2, log_norm=self.log_norm)
+        return self._tables[dev]
+
+    def _check(self, m, w):
+        if m.ndim != 2 or m.shape[1] != self.n_data:
+            raise ValueError('the model output must have shape (n, %d), not '
+                             '%s' % (self.n_data, tuple(m.shape)))
+        if w.ndim != 2 or tuple(w.shape) != (m.shape[0], self._width):
+            raise ValueError('the noise must have shape (%d, %d), not %s' %
+                             (m.shape[0], self._width, tuple(w.shape)))
+
+    @staticmethod
+    def _rows(t, width):
+        """``t`` on the device, as it is where its rows can be read in place
+        and contiguous otherwise."""
+        t = t if t.is_cuda else t.cuda()
+        in_place = (width == 1 or t.stride(1) == 1) and \
+            (t.shape[0] <= 1 or t.stride(0) >= width)
+        return t if in_place else t.contiguous()
+
+    def from_model(self, m, w):
+        """log L of the rows of an (n, P) float64 model output and its noise
+        ((n, 3) or (n, P)): cuda tensors in, a cuda tensor out; numpy in,
+        numpy out."""
+        tensors = isinstance(m, torch.Tensor), isinstance(w, torch.Tensor)
+        if tensors[0] != tensors[1]:
+            raise ValueError('the model output and the noise must both be '
+                             'torch tensors or both numpy arrays')
+        if tensors[0]:
+            for t in (m, w):
+                if t.dtype != torch.float64:
+                    raise ValueError('the model output and the noise must be '
+                                     'float64, not %s' % t.dtype)
+            self._check(m, w)
+            mode = device.NOISE_ROW if self.noise == 'row' else \
+                device.NOISE_FULL
+            return self._table().loglike(
+                self._rows(m, self.n_data), self._rows(w, self._width), mode)
+        m, w = np.asarray(m), np.asarray(w)
+        for t in (m, w):
+            if t.dtype != np.float64:
+                raise ValueError('the model output and the noise must be '
+                                 'float64, not %s' % t.dtype)
+        self._check(m, w)
+        return self.from_model(
+            torch.from_numpy(np.ascontiguousarray(m)).cuda(),
+            torch.from_numpy(np.ascontiguousarray(w)).cuda()).cpu().numpy()
+
+    def __call__(self, x):
+        if isinstance(x, torch.Tensor):
+            return self.from_model(*self.model(x))
+        xs = device.as_device_points(x)
+        return self.from_model(*self.model(xs)).cpu().numpy()
+
+    def numpy_variance(self, m, w):
+        """The (n, P) variances v_ij of an (n, P) model output and its noise,
+        in pure numpy and as they come: a v outside (0, +inf) is not marked
+        here."""
+        m, w = np.asarray(m, float), np.asarray(w, float)
+        self._check(m, w)
+        with np.errstate(all='ignore'):
+            if self.noise == 'row':
+                return w[:, 0:1] * self._sigma2 + w[:, 1:2] + \
+                    w[:, 2:3] * (m * m)
+            return self._sigma2 + w
+
+    def numpy_terms(self, m, w):
+        """The (n, P) pair (chi^2 terms (m - d)^2 / v, log v) in pure numpy;
+        both are NaN where m is not finite or v is not in (0, +inf)."""
+        m = np.asarray(m, float)
+        v = self.numpy_variance(m, w)
+        with np.errstate(all='ignore'):
+            good = np.isfinite(m) & (v > 0) & (v < np.inf)
+            vg = np.where(good, v, 1.0)
+            r = np.where(good, m, 0.0) - self.data
+            chi = np.where(good, r * r / vg, np.nan)
+            log_v = np.where(good, np.log(vg), np.nan)
+        return chi, log_v
+
+    def numpy_from_model(self, m, w):
+        """Pure-numpy evaluation of an (n, P) model output and its noise (CPU
+        baseline / oracle runs / tests)."""
+        chi, log_v = self.numpy_terms(m, w)
+        bad = np.isnan(chi)
+        out = self.log_norm - 0.5 * np.sum(np.where(bad, 0.0, chi + log_v),
+                                           axis=1)
+        out[np.any(bad, axis=1)] = np.nan
+        return out
+
+    def numpy(self, x):
+        """Pure-numpy twin of a call: the model runs on the CPU."""
+        x = np.atleast_2d(np.asarray(x, float))
+        m, w = self.model(torch.from_numpy(x))
+        if isinstance(m, torch.Tensor):
+            m = m.detach().cpu().numpy()
+        if isinstance(w, torch.Tensor):
+            w = w.detach().cpu().numpy()
+        return self.numpy_from_model(m, w)
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state['_tables'] = {}
+        return state
+
+
 class RosenbrockLikelihood:
     """Rosenbrock function on x = low + (high - low) u (BASELINE config 3):
     log L = -sum_i [a (x_{i+1} - x_i^2)^2 + (1 - x_i)^2] --
