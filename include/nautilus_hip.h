@@ -285,6 +285,28 @@ int nb_trainer_destroy(nb_trainer* t);
 int nb_philox_uniform(uint64_t seed, uint64_t offset, uint32_t block,
                       uint32_t tag, int64_t n, double* u_dev, void* stream);
 
+/* The Box-Muller arithmetic of nb_propose word by word, for tests (the device
+ * functions of nb_draw.h themselves; u(w) = (w + 1/2) / 2^32, DESIGN.md "RNG
+ * contract").  nb_draw_words: out_dev[5 i ..] = log u(w0[i]) as the draw
+ * computes it, its sin 2 pi u(w1[i]), its cos 2 pi u(w1[i]), and the pair of
+ * normals z0, z1 the draw makes of the words (w0[i], w1[i]).
+ * nb_draw_sweep: the words first .. first + count - 1 (first + count <= 2^32)
+ * in chunks [c chunk_words, (c + 1) chunk_words), chunk_words a positive
+ * multiple of 4096, n_chunks = (first + count - 1) / chunk_words - first /
+ * chunk_words + 1 <= NB_DRAW_SWEEP_MAX_CHUNKS of them.  stats_dev holds 3 + 3
+ * n_chunks words, zeroed here: [0], [1], [2] = the number of words whose log
+ * is not a finite negative number, whose sine, whose cosine is not in [-1, 1];
+ * then n_chunks words each for the log, the sine and the cosine: the largest
+ * difference, inside the chunk, from the device library's log(u) resp.
+ * sincospi(2 u) in ulp of the library's value, as the bits of a float in the
+ * high half, and the word where it occurs in the low half (the largest such
+ * word; +inf for a NaN).                                                    */
+#define NB_DRAW_SWEEP_MAX_CHUNKS 65536
+int nb_draw_words(const uint32_t* w0_dev, const uint32_t* w1_dev, int64_t n,
+                  double* out_dev, void* stream);
+int nb_draw_sweep(uint64_t first, uint64_t count, uint64_t chunk_words,
+                  uint64_t* stats_dev, void* stream);
+
 /* Measurement hook for bench.py: when non-NULL, every bound-evaluation launch
  * adds to counters_dev[0..2] the number of point evaluations it performed
  * (outer-member tests, neural-ellipsoid transforms, emulator forward passes x

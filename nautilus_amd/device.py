@@ -1073,6 +1073,43 @@ def philox_uniform(seed, offset, block, tag, n):
     return u
 
 
+def draw_words(w0, w1):
+    """The Box-Muller arithmetic of the proposal draw for the 32-bit words
+    ``w0`` (log) and ``w1`` (sine, cosine): rows (log, sin, cos, z0, z1)."""
+    lib = _lib.load()
+    w0 = np.ascontiguousarray(w0, dtype=np.uint32)
+    w1 = np.ascontiguousarray(w1, dtype=np.uint32)
+    if w0.shape != w1.shape or w0.ndim != 1:
+        raise ValueError('two vectors of words of one length')
+    d0 = torch.from_numpy(w0.view(np.int32)).cuda()
+    d1 = torch.from_numpy(w1.view(np.int32)).cuda()
+    out = torch.empty((len(w0), 5), dtype=torch.float64, device='cuda')
+    _lib.check(lib.nb_draw_words(_ptr(d0), _ptr(d1), len(w0), _ptr(out),
+                                 _stream()))
+    torch.cuda.current_stream().synchronize()    # d0, d1 die here
+    return out
+
+
+def draw_sweep(first, count, chunk_words):
+    """nb_draw_sweep over the words first .. first + count - 1: the numbers
+    of bad words (log, sin, cos), and per function and chunk the largest
+    difference from the device library in ulp, (3, n_chunks) float32, and the
+    word it occurs at, (3, n_chunks) uint32; chunk 0 is the one of ``first``."""
+    lib = _lib.load()
+    n_chunks = 0
+    if count > 0 and chunk_words > 0:
+        n_chunks = (first + count - 1) // chunk_words - first // chunk_words + 1
+    stats = torch.empty(3 + 3 * max(n_chunks, 0), dtype=torch.int64,
+                        device='cuda')
+    _lib.check(lib.nb_draw_sweep(first, count, chunk_words, _ptr(stats),
+                                 _stream()))
+    host = stats.cpu().numpy().view(np.uint64)
+    keys = host[3:].reshape(3, n_chunks)
+    return (host[:3].astype(np.int64),
+            (keys >> np.uint64(32)).astype(np.uint32).view(np.float32),
+            (keys & np.uint64(0xffffffff)).astype(np.uint32))
+
+
 def mfma_f64_peak(iters=20000):
     lib = _lib.load()
     out = C.c_double(0.0)

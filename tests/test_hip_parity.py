@@ -37,8 +37,11 @@ def _ell_from_golden(g):
 
 def test_philox_matches_oracle(dev):
     from oracle import philox
+    # (the last two: the low word of offset + i wraps inside the launch)
     for seed, off, block, tag in [(0, 0, 0, 0), (2**40 + 17, 2**33 + 5, 3, 1),
-                                  (12345, 999, 7, 2)]:
+                                  (12345, 999, 7, 2),
+                                  (2**35 + 9, 2**32 - 2048, 2, 1),
+                                  (7, 3 * 2**32 - 2048, 0, 0)]:
         u = dev.philox_uniform(seed, off, block, tag, 4096).cpu().numpy()
         g = np.uint64(off) + np.arange(4096, dtype=np.uint64)
         u0, u1 = philox.uniform_pair(seed, g, block, tag)
@@ -202,6 +205,48 @@ def test_union_proposals_match_oracle(dev, name, mixture):
     assert abs(log_v - float(g['log_v'])) < 0.1
 
 
+@pytest.mark.parametrize('name', ['union_K4_D8', 'single_D20'])
+def test_proposals_across_a_carry_of_the_index(dev, name):
+    """The Philox counter of proposal i is the 64-bit offset + i.  A launch
+    whose indices cross 2^32 (a long run takes a bound's offset past it):
+    proposals and acceptance flags against the oracle, for a union that draws
+    the member (K = 4) and for a single ellipsoid (K = 1: no member draw, B
+    through scalar operands); and the launch split at a row that is no
+    multiple of 64 gives the same bits.  A counter whose low word wraps
+    without the carry would repeat 3000 earlier proposals."""
+    from oracle import bounds_oracle as bo
+    from oracle import philox
+    if name.startswith('union'):
+        u = _union_from_golden(load_golden(name), True)
+    else:       # one ellipsoid, part of it outside the unit cube
+        rng = np.random.default_rng(20)
+        centre = np.full(20, 0.5)
+        centre[0] = 0.8
+        u = bo.OUnion.from_members([bo.OEllipsoid.from_params(
+            centre, np.tril(rng.normal(size=(20, 20)) * 0.02) +
+            np.eye(20) * 0.4)], unit=True)
+    b = upload(u)
+    assert b.n_members == len(u.bounds)
+    seed, n, a = 77, 6000, 2987
+    # (the second one: the high word is not zero before the carry either)
+    for offset in (2**32 - 3000, 5 * 2**32 - 3000):
+        x = b.propose(seed, offset, n)
+        flags = b.accept(seed, offset, x).cpu().numpy()
+        x_o, keep_o, _ = philox.union_propose(u, seed, offset, n)
+        assert np.allclose(x.cpu().numpy(), x_o, rtol=0, atol=1e-12)
+        assert np.array_equal((flags & 1).astype(bool), keep_o)
+        assert 0 < keep_o.sum() < n
+        # (the oracle's own stream does not repeat after the carry)
+        x_w, _, _ = philox.union_propose(u, seed, offset >> 32 << 32, 3000)
+        assert np.abs(x_o[3000:] - x_w).max() > 1e-3
+        head = b.propose(seed, offset, a)
+        tail = b.propose(seed, offset + a, n - a)
+        assert torch.equal(torch.cat([head, tail]), x)
+        f_head = b.accept(seed, offset, head).cpu().numpy()
+        f_tail = b.accept(seed, offset + a, tail).cpu().numpy()
+        assert np.array_equal(np.concatenate([f_head, f_tail]), flags)
+
+
 def test_unit_cube(dev):
     from oracle import bounds_oracle as bo
     from oracle import philox
@@ -290,24 +335,12 @@ def test_neural_bound_large_dims(dev, d, e):
                           any_o[~edge])
 
 
-@pytest.mark.parametrize('d,e,k_outer', [
-    (1, 1, 1), (3, 2, 1), (15, 1, 1), (16, 2, 1), (17, 1, 0), (31, 2, 1),
-    (32, 1, 1), (33, 3, 1), (47, 1, 1), (48, 2, 0), (49, 1, 1), (50, 4, 1),
-    (62, 2, 1), (63, 1, 1), (64, 2, 1), (65, 1, 1), (79, 2, 1), (80, 1, 0),
-    (81, 2, 1), (96, 1, 1), (100, 8, 1), (112, 2, 1), (127, 1, 1),
-    (128, 2, 1)])
-def test_pipelined_accept_and_score(dev, d, e, k_outer):
-    """nb_accept / nb_neural_score of a bound with ONE neural bound and at
-    most one outer member run through the pipelined kernel (nb_eval_fast.hip)
-    for every n_dim <= 128 -- every (DT, KT1) instantiation, n_dim = 16 DT
-    included, where layer 1 needs one more k-tile, layer 1 in one stage and
-    in two K chunks (n_dim >= 80).  Launch sizes: below one pass, ragged
-    tails, and more 128-point passes than workgroups (the points of the next
-    pass are prefetched during the last stage).  Oracle: union.py:313-319 +
-    neural.py:115-126 on the same Philox stream."""
+def _pipelined_bound(dev, d, e, k_outer):
+    """One neural bound of e networks in n_dim = d under at most one outer
+    member: (device bound, outer union or None, neural bound, its ellipsoid,
+    emulator, centre, B, the generator that made them)."""
     from oracle import bounds_oracle as bo
     from oracle import mlp_oracle as mo
-    from oracle import philox
     rng = np.random.default_rng(77 * d + e)
     nets = [mo.glorot_init(d, i)[:2] for i in range(e)]
     mean, scale = rng.normal(size=d) * 0.1, rng.uniform(0.5, 1.5, d)
@@ -330,6 +363,27 @@ def test_pipelined_accept_and_score(dev, d, e, k_outer):
     else:       # unit cube as the only outer bound
         from helpers import neural_from_oracle
         b = dev.DeviceBound(d, [], None, True, [neural_from_oracle(nb)])
+    return b, outer, nb, ell, emu, centre, b_mat, rng
+
+
+@pytest.mark.parametrize('d,e,k_outer', [
+    (1, 1, 1), (3, 2, 1), (15, 1, 1), (16, 2, 1), (17, 1, 0), (31, 2, 1),
+    (32, 1, 1), (33, 3, 1), (47, 1, 1), (48, 2, 0), (49, 1, 1), (50, 4, 1),
+    (62, 2, 1), (63, 1, 1), (64, 2, 1), (65, 1, 1), (79, 2, 1), (80, 1, 0),
+    (81, 2, 1), (96, 1, 1), (100, 8, 1), (112, 2, 1), (127, 1, 1),
+    (128, 2, 1)])
+def test_pipelined_accept_and_score(dev, d, e, k_outer):
+    """nb_accept / nb_neural_score of a bound with ONE neural bound and at
+    most one outer member run through the pipelined kernel (nb_eval_fast.hip)
+    for every n_dim <= 128 -- every (DT, KT1) instantiation, n_dim = 16 DT
+    included, where layer 1 needs one more k-tile, layer 1 in one stage and
+    in two K chunks (n_dim >= 80).  Launch sizes: below one pass, ragged
+    tails, and more 128-point passes than workgroups (the points of the next
+    pass are prefetched during the last stage).  Oracle: union.py:313-319 +
+    neural.py:115-126 on the same Philox stream."""
+    from oracle import philox
+    b, outer, nb, ell, emu, centre, b_mat, rng = _pipelined_bound(
+        dev, d, e, k_outer)
     seed, offset = 11 + d, 10**11 + 3
     for n in (1, 127, 128, 129, 5000, 40000):
         if k_outer:
@@ -360,21 +414,11 @@ def test_pipelined_accept_and_score(dev, d, e, k_outer):
             assert 0 < want.mean() < 1
 
 
-# (n_dim mod 16 in 1..4 -- 20, 33, 50, 67, 100: the last row tile of every
-# ellipsoid test runs on the 4-row matrix instruction, nb_cand.hip StepTable)
-@pytest.mark.parametrize('d,k,m', [(20, 3, 2), (50, 2, 3), (33, 2, 2),
-                                   (67, 2, 2), (100, 2, 2), (53, 2, 2)])
-def test_two_stage_large_launch(dev, d, k, m):
-    """Bounds with several outer members and several neural bounds go through
-    the two device-side stages (nb_cand.hip: geometric tests + candidate
-    lists, then ONE batched emulator launch of nb_eval_fast.hip).  The launch
-    size decides how the points are dealt out over the wavefronts and how the
-    candidate lists are laid out: the flags of the same proposals must not
-    depend on it, and both agree with the oracle (union.py:305-327,
-    nautilus.py:146-169 on the same Philox stream)."""
+def _two_stage_bound(d, k, m):
+    """k outer members and m neural bounds of two networks each in n_dim = d:
+    (device bound, outer union, oracle bound, neural bounds)."""
     from oracle import bounds_oracle as bo
     from oracle import mlp_oracle as mo
-    from oracle import philox
     rng = np.random.default_rng(5 * d + k)
     centres = 0.5 + 0.04 * rng.normal(size=(max(k, m), d))
     members, neural = [], []
@@ -398,6 +442,23 @@ def test_two_stage_large_launch(dev, d, k, m):
     outer = bo.OUnion.from_members(members, unit=True)
     ob = bo.ONautilus.from_parts(outer, neural)
     b = upload(ob)
+    return b, outer, ob, neural
+
+
+# (n_dim mod 16 in 1..4 -- 20, 33, 50, 67, 100: the last row tile of every
+# ellipsoid test runs on the 4-row matrix instruction, nb_cand.hip StepTable)
+@pytest.mark.parametrize('d,k,m', [(20, 3, 2), (50, 2, 3), (33, 2, 2),
+                                   (67, 2, 2), (100, 2, 2), (53, 2, 2)])
+def test_two_stage_large_launch(dev, d, k, m):
+    """Bounds with several outer members and several neural bounds go through
+    the two device-side stages (nb_cand.hip: geometric tests + candidate
+    lists, then ONE batched emulator launch of nb_eval_fast.hip).  The launch
+    size decides how the points are dealt out over the wavefronts and how the
+    candidate lists are laid out: the flags of the same proposals must not
+    depend on it, and both agree with the oracle (union.py:305-327,
+    nautilus.py:146-169 on the same Philox stream)."""
+    from oracle import philox
+    b, outer, ob, neural = _two_stage_bound(d, k, m)
     seed, offset, n = 31 + d, 10**10 + 7, 150000
     xd = b.propose(seed, offset, n)
     big = b.accept(seed, offset, xd).cpu().numpy()
@@ -428,6 +489,37 @@ def test_two_stage_large_launch(dev, d, k, m):
     want_in = ob.contains(x)
     assert np.array_equal(inside_big[lo:hi][~score_edge],
                           want_in[~score_edge])
+
+
+@pytest.mark.parametrize('route', ['fused', 'staged'])
+def test_acceptance_across_a_carry_of_the_index(dev, route):
+    """The acceptance uniform of proposal i comes from the 64-bit counter
+    offset + i as well, in the fused kernel (nb_eval_fast.hip: one neural
+    bound, one outer member) and in the first of the two stages (nb_cand.hip:
+    three overlapping outer members, so that u > 1 - 1/k decides): bit 0 of
+    the flags against the oracle for a launch whose indices cross 2^32."""
+    from oracle import philox
+    if route == 'fused':
+        b, outer = _pipelined_bound(dev, 17, 1, 1)[:2]
+        b.dense_need = 1.0
+    else:
+        b, outer = _two_stage_bound(20, 3, 2)[:2]
+    seed, offset, n = 6, 2**32 - 3000, 6000
+    x, keep, k = philox.union_propose(outer, seed, offset, n)
+    xd = b.propose(seed, offset, n)
+    assert np.allclose(xd.cpu().numpy(), x, rtol=0, atol=1e-12)
+    flags = b.accept(seed, offset, xd).cpu().numpy()
+    assert np.array_equal(flags & 1, keep.astype(np.uint8))
+    assert 0 < keep.sum() < n
+    if route == 'staged':
+        # the draw decides, and with the uniforms of a 32-bit counter it would
+        # decide differently (overlaps are rare in 20 dimensions: 14 rows)
+        g = np.uint64(offset) + np.arange(n, dtype=np.uint64)
+        _, u_acc = philox.uniform_pair(seed, g, 0, philox.TAG_CTRL)
+        _, u_low = philox.uniform_pair(seed, g & philox.MASK, 0,
+                                       philox.TAG_CTRL)
+        assert np.any(~keep & (k > 1))
+        assert np.any((u_low > 1 - 1.0 / k) != (u_acc > 1 - 1.0 / k))
 
 
 def test_accept_routes_agree(dev):
