@@ -144,10 +144,14 @@ def test_nested_nautilus_bounds(d, e, periodic):
 @pytest.mark.parametrize('d,e', [(12, 2), (33, 1), (40, 4), (48, 2), (50, 4),
                                  (64, 1), (70, 2), (100, 1)])
 def test_nautilus_sample_dims(d, e):
-    """NautilusBound.sample (nautilus.py:199-224) in every size class of the
-    proposal path of the evaluation kernel (two / one tile per wavefront, the
-    pre-issued copies up to n_dim = 48): accepted points and counters against
-    the oracle, plus the emulator scores of the proposals."""
+    """NautilusBound.sample (nautilus.py:199-224) over the size classes of the
+    acceptance kernels: accepted points and counters against the oracle, plus
+    the emulator scores of the proposals.  The first launch of a bound always
+    takes the staged route (nb_cand.hip + one BATCH launch of
+    nb_eval_fast.hip); with ``dense_need`` pinned the same launch goes
+    through the fused kernel and returns the same counters and points."""
+    import torch
+    from nautilus_amd import device
     from oracle import bounds_oracle as bo
     from oracle import mlp_oracle as mo
     from oracle import philox
@@ -168,8 +172,17 @@ def test_nautilus_sample_dims(d, e):
     nb.score_predict_min = float(np.median(score_all))
     ob = bo.ONautilus.from_parts(outer, [nb])
     b = upload(ob)
+    before = dict(device.DISPATCHES)
     pts, counts = b.sample_launch(seed, offset, n)
     c = counts.cpu().numpy()
+    assert device.DISPATCHES['nb_cand_kernel'] == before['nb_cand_kernel'] + 1
+    b.dense_need = 1.0
+    before = dict(device.DISPATCHES)
+    pts_f, counts_f = b.sample_launch(seed, offset, n)
+    assert device.DISPATCHES == dict(
+        before, nb_eval_fast_kernel=before['nb_eval_fast_kernel'] + 1)
+    assert torch.equal(counts_f, counts)
+    assert torch.equal(pts_f[:int(c[1])], pts[:int(c[1])])
     pts_o, cnt_o = philox.nautilus_sample(ob, seed, offset, n)
     n_edge = int(near_boundary(score_all, nb.score_predict_min - 1e-9,
                                1e-9).sum())

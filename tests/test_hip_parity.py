@@ -374,16 +374,23 @@ def _pipelined_bound(dev, d, e, k_outer):
     (128, 2, 1)])
 def test_pipelined_accept_and_score(dev, d, e, k_outer):
     """nb_accept / nb_neural_score of a bound with ONE neural bound and at
-    most one outer member run through the pipelined kernel (nb_eval_fast.hip)
-    for every n_dim <= 128 -- every (DT, KT1) instantiation, n_dim = 16 DT
+    most one outer member for every n_dim <= 128 -- every (DT, KT1)
+    instantiation of the pipelined kernel (nb_eval_fast.hip), n_dim = 16 DT
     included, where layer 1 needs one more k-tile, layer 1 in one stage and
-    in two K chunks (n_dim >= 80).  Launch sizes: below one pass, ragged
-    tails, and more 128-point passes than workgroups (the points of the next
-    pass are prefetched during the last stage).  Oracle: union.py:313-319 +
-    neural.py:115-126 on the same Philox stream."""
+    in two K chunks (n_dim >= 80).  ``neural_score`` always runs that kernel;
+    ``accept`` picks its route from the bound's first launch, so the route is
+    PINNED here (``dense_need``) and read back from ``device.DISPATCHES``:
+    every launch through the fused kernel, then through the staged route
+    (nb_cand.hip + one BATCH launch of the pipelined kernel), same checks.
+    (Left to the first launch -- one proposal -- sixteen of these cases took
+    the staged route in every ``accept``.)  Launch sizes: below one pass,
+    ragged tails, and more 128-point passes than workgroups (the points of
+    the next pass are prefetched during the last stage).  Oracle:
+    union.py:313-319 + neural.py:115-126 on the same Philox stream."""
     from oracle import philox
     b, outer, nb, ell, emu, centre, b_mat, rng = _pipelined_bound(
         dev, d, e, k_outer)
+    assert b.n_neural == 1 and b.n_members <= 1 and b.n_networks == e
     seed, offset = 11 + d, 10**11 + 3
     for n in (1, 127, 128, 129, 5000, 40000):
         if k_outer:
@@ -399,7 +406,6 @@ def test_pipelined_accept_and_score(dev, d, e, k_outer):
         r2, score = b.neural_score(xd)
         assert np.allclose(r2.cpu().numpy(), r2_o, rtol=1e-12, atol=1e-13)
         assert np.allclose(score.cpu().numpy(), score_o, rtol=0, atol=1e-10)
-        flags = b.accept(seed, offset, xd).cpu().numpy()
         g = np.uint64(offset) + np.arange(n, dtype=np.uint64)
         _, u_acc = philox.uniform_pair(seed, g, 0, philox.TAG_CTRL)
         in_cube = np.all((x >= 0) & (x < 1), axis=1)
@@ -407,9 +413,20 @@ def test_pipelined_accept_and_score(dev, d, e, k_outer):
         inside = (r2_o < 1) & (score_o > nb.score_predict_min - 1e-9)
         edge = (near_boundary(score_o, nb.score_predict_min - 1e-9, 1e-9) |
                 near_boundary(r2_o, 1.0, 1e-12))
-        assert np.array_equal(flags & 1, keep.astype(np.uint8))
         want = (keep & inside).astype(np.uint8)
-        assert np.array_equal((flags >> 1)[~edge], want[~edge])
+        # the fused kernel, then the staged route: (dense_need, launches of
+        # nb_eval_fast_kernel, of nb_cand_kernel)
+        for need, n_fast, n_cand in ((1.0, 1, 0), (0.0, 1, 1)):
+            b.dense_need = need
+            before = dict(dev.DISPATCHES)
+            flags = b.accept(seed, offset, xd).cpu().numpy()
+            assert dev.DISPATCHES['nb_eval_fast_kernel'] == \
+                before['nb_eval_fast_kernel'] + n_fast
+            assert dev.DISPATCHES['nb_cand_kernel'] == \
+                before['nb_cand_kernel'] + n_cand
+            assert b.dense_need == need
+            assert np.array_equal(flags & 1, keep.astype(np.uint8))
+            assert np.array_equal((flags >> 1)[~edge], want[~edge])
         if n >= 5000 and d <= 64:         # (the test data decides both ways)
             assert 0 < want.mean() < 1
 
