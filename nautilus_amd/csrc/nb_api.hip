@@ -282,6 +282,32 @@ void fill_net(double* net, int n_dim, int kt1, const double* const* coefs,
 
 inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 
+// The tail of every table handle: one device allocation filled from the host
+// once (freed again if the copy fails) ...
+int nb_upload_table(const std::vector<double>& host, double** dev,
+                    const char* what) {
+  const size_t bytes = host.size() * sizeof(double);
+  hipError_t e = hipMalloc((void**)dev, bytes);
+  if (e == hipSuccess)
+    e = hipMemcpy(*dev, host.data(), bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    nb_set_error("%s upload failed: %s", what, hipGetErrorString(e));
+    if (*dev != nullptr) (void)hipFree(*dev);
+    *dev = nullptr;
+    return NB_ERR_HIP;
+  }
+  return NB_OK;
+}
+
+// ... and released with its handle
+template <class H>
+int nb_destroy_table(H* h) {
+  if (h == nullptr) return NB_OK;
+  (void)hipFree(h->dev);
+  delete h;
+  return NB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1242,10 +1268,7 @@ int nb_prior_table_create(int32_t n_dim, const uint8_t* kind,
 }
 
 int nb_prior_table_destroy(nb_prior_table* table) {
-  if (table == nullptr) return NB_OK;
-  (void)hipFree(table->dev);
-  delete table;
-  return NB_OK;
+  return nb_destroy_table(table);
 }
 
 int nb_prior_table_transform(const nb_prior_table* table, const double* u,
@@ -1348,29 +1371,18 @@ int nb_mixture_create(int32_t n_dim, int32_t n_components, const double* means,
     for (int h = 0; h < n_dim; ++h) tail[h] = mu[h];
     tail[16 * dt] = log_coef[c];
   }
+  double* dev = nullptr;
+  const int rc = nb_upload_table(host, &dev, "mixture");
+  if (rc != NB_OK) return rc;
   nb_mixture* m = new nb_mixture;
+  m->dev = dev;
   m->n_dim = n_dim;
   m->n_comp = n_components;
-  const size_t bytes = host.size() * sizeof(double);
-  hipError_t e = hipMalloc((void**)&m->dev, bytes);
-  if (e == hipSuccess)
-    e = hipMemcpy(m->dev, host.data(), bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    nb_set_error("mixture upload failed: %s", hipGetErrorString(e));
-    if (m->dev != nullptr) (void)hipFree(m->dev);
-    delete m;
-    return NB_ERR_HIP;
-  }
   *out = m;
   return NB_OK;
 }
 
-int nb_mixture_destroy(nb_mixture* mix) {
-  if (mix == nullptr) return NB_OK;
-  (void)hipFree(mix->dev);
-  delete mix;
-  return NB_OK;
-}
+int nb_mixture_destroy(nb_mixture* mix) { return nb_destroy_table(mix); }
 
 int nb_mixture_loglike(const nb_mixture* mix, const double* x, int64_t n,
                        double* out, int32_t* label, void* stream) {
@@ -1460,30 +1472,19 @@ int nb_chi2_create(int32_t n_data, const double* data, const double* chol_inv,
         }
     }
   }
+  double* dev = nullptr;
+  const int rc = nb_upload_table(host, &dev, "data likelihood");
+  if (rc != NB_OK) return rc;
   nb_chi2* c = new nb_chi2;
+  c->dev = dev;
   c->n_data = n_data;
   c->diag = inv_sigma != nullptr;
   c->log_norm = log_norm;
-  const size_t bytes = host.size() * sizeof(double);
-  hipError_t e = hipMalloc((void**)&c->dev, bytes);
-  if (e == hipSuccess)
-    e = hipMemcpy(c->dev, host.data(), bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    nb_set_error("data likelihood upload failed: %s", hipGetErrorString(e));
-    if (c->dev != nullptr) (void)hipFree(c->dev);
-    delete c;
-    return NB_ERR_HIP;
-  }
   *out = c;
   return NB_OK;
 }
 
-int nb_chi2_destroy(nb_chi2* h) {
-  if (h == nullptr) return NB_OK;
-  (void)hipFree(h->dev);
-  delete h;
-  return NB_OK;
-}
+int nb_chi2_destroy(nb_chi2* h) { return nb_destroy_table(h); }
 
 int nb_chi2_loglike(const nb_chi2* h, const double* model, int64_t ld,
                     int64_t n, double* out, void* stream) {
@@ -1552,29 +1553,18 @@ int nb_poisson_create(int32_t n_data, const double* counts,
     host[2 * p + j] = e;
     host[3 * p + j] = b;
   }
+  double* dev = nullptr;
+  const int rc = nb_upload_table(host, &dev, "Poisson likelihood");
+  if (rc != NB_OK) return rc;
   nb_poisson* c = new nb_poisson;
+  c->dev = dev;
   c->n_data = n_data;
   c->log_const = log_const;
-  const size_t bytes = host.size() * sizeof(double);
-  hipError_t e = hipMalloc((void**)&c->dev, bytes);
-  if (e == hipSuccess)
-    e = hipMemcpy(c->dev, host.data(), bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    nb_set_error("Poisson likelihood upload failed: %s", hipGetErrorString(e));
-    if (c->dev != nullptr) (void)hipFree(c->dev);
-    delete c;
-    return NB_ERR_HIP;
-  }
   *out = c;
   return NB_OK;
 }
 
-int nb_poisson_destroy(nb_poisson* h) {
-  if (h == nullptr) return NB_OK;
-  (void)hipFree(h->dev);
-  delete h;
-  return NB_OK;
-}
+int nb_poisson_destroy(nb_poisson* h) { return nb_destroy_table(h); }
 
 int nb_poisson_loglike(const nb_poisson* h, const double* model, int64_t ld,
                        int64_t n, double* out, void* stream) {
@@ -1655,31 +1645,19 @@ int nb_fold_poisson_create(int32_t n_data, int32_t n_src, const double* counts,
           }
         }
   }
+  double* dev = nullptr;
+  const int rc = nb_upload_table(host, &dev, "folded Poisson likelihood");
+  if (rc != NB_OK) return rc;
   nb_fold_poisson* f = new nb_fold_poisson;
+  f->dev = dev;
   f->n_data = n_data;
   f->n_src = n_src;
   f->log_const = log_const;
-  const size_t bytes = host.size() * sizeof(double);
-  hipError_t e = hipMalloc((void**)&f->dev, bytes);
-  if (e == hipSuccess)
-    e = hipMemcpy(f->dev, host.data(), bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    nb_set_error("folded Poisson likelihood upload failed: %s",
-                 hipGetErrorString(e));
-    if (f->dev != nullptr) (void)hipFree(f->dev);
-    delete f;
-    return NB_ERR_HIP;
-  }
   *out = f;
   return NB_OK;
 }
 
-int nb_fold_poisson_destroy(nb_fold_poisson* h) {
-  if (h == nullptr) return NB_OK;
-  (void)hipFree(h->dev);
-  delete h;
-  return NB_OK;
-}
+int nb_fold_poisson_destroy(nb_fold_poisson* h) { return nb_destroy_table(h); }
 
 int nb_fold_poisson_loglike(const nb_fold_poisson* h, const double* src,
                             int64_t ld, int64_t n, double* out, void* stream) {
@@ -1723,29 +1701,18 @@ int nb_noise_create(int32_t n_data, const double* data, const double* sigma2,
     }
     host[p + j] = sigma2[j];
   }
+  double* dev = nullptr;
+  const int rc = nb_upload_table(host, &dev, "noise likelihood");
+  if (rc != NB_OK) return rc;
   nb_noise* c = new nb_noise;
+  c->dev = dev;
   c->n_data = n_data;
   c->log_norm = log_norm;
-  const size_t bytes = host.size() * sizeof(double);
-  hipError_t e = hipMalloc((void**)&c->dev, bytes);
-  if (e == hipSuccess)
-    e = hipMemcpy(c->dev, host.data(), bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    nb_set_error("noise likelihood upload failed: %s", hipGetErrorString(e));
-    if (c->dev != nullptr) (void)hipFree(c->dev);
-    delete c;
-    return NB_ERR_HIP;
-  }
   *out = c;
   return NB_OK;
 }
 
-int nb_noise_destroy(nb_noise* h) {
-  if (h == nullptr) return NB_OK;
-  (void)hipFree(h->dev);
-  delete h;
-  return NB_OK;
-}
+int nb_noise_destroy(nb_noise* h) { return nb_destroy_table(h); }
 
 int nb_noise_loglike(const nb_noise* h, int32_t mode, const double* model,
                      int64_t ld, const double* noise, int64_t ld_noise,

@@ -39,6 +39,7 @@
 //
 // The diagonal case (sigma) is a separate memory-bound kernel below.
 #include "nb_common.h"
+#include "nb_lds_copy.h"
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 
@@ -47,24 +48,6 @@ namespace {
 constexpr int CH_WAVES = 8;                     // wavefronts of a workgroup
 constexpr int CH_RT = NB_CHI2_PANEL / CH_WAVES; // row tiles per wavefront
 static_assert(CH_RT == 2, "row tiles w and 8 + w");
-
-typedef const void __attribute__((address_space(1))) * ch_gptr;
-typedef void __attribute__((address_space(3))) * ch_lptr;
-
-// s_waitcnt vmcnt(0) (expcnt and lgkmcnt left at their maxima)
-__device__ __forceinline__ void ch_wait_copies() {
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-}
-
-// asynchronous global -> LDS copy of n_tiles operand tiles by the whole
-// workgroup in 1 KB pieces (destination = uniform base + lane * 16)
-__device__ __forceinline__ void ch_copy(const nb_gd* __restrict__ src,
-                                        double* dst, int n_tiles, int wave,
-                                        int lane) {
-  for (int c = wave; c < 2 * n_tiles; c += CH_WAVES)
-    __builtin_amdgcn_global_load_lds((ch_gptr)(src + c * 128 + 2 * lane),
-                                     (ch_lptr)(dst + c * 128), 16, 0, 0);
-}
 
 // blob: d zero padded to 16 DT doubles (nb_chi2_w_offset), then for every
 // panel p and k-tile kt <= last row tile of p the panel's row tiles as 16x16
@@ -140,7 +123,7 @@ nb_chi2_kernel(const double* __restrict__ blob, int n_data,
   // w_nxt / r_nxt.  Returns false after the last chunk.
   auto step = [&](const double* w_cur, const double* r_cur, double* w_nxt,
                   double* r_nxt) __attribute__((always_inline)) -> bool {
-    ch_wait_copies();
+    nb_wait_copies();
     __syncthreads();
     const int nkt = NB_CHI2_PANEL * panel + nrt;       // k-tiles of the panel
     const bool last_of_panel = kt + 1 == nkt;
@@ -151,7 +134,7 @@ nb_chi2_kernel(const double* __restrict__ blob, int n_data,
     const int nrt_n = left < NB_CHI2_PANEL ? left : NB_CHI2_PANEL;
     const nb_gd* wsrc_n = wsrc + (size_t)nrt * NB_TILE;
     if (more) {
-      ch_copy(wsrc_n, w_nxt, nrt_n, wave, lane);
+      nb_copy_tiles<CH_WAVES>(wsrc_n, w_nxt, nrt_n, wave, lane);
       if (stager) load_r(kt_n);
     }
 
@@ -198,7 +181,7 @@ nb_chi2_kernel(const double* __restrict__ blob, int n_data,
   };
 
   // chunk (0, 0) into the a buffers
-  ch_copy(wsrc, w_a, nrt, wave, lane);
+  nb_copy_tiles<CH_WAVES>(wsrc, w_a, nrt, wave, lane);
   if (stager) {
     load_r(0);
     write_r(r_a, 0);

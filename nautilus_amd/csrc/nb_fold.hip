@@ -47,6 +47,7 @@
 // skipped.  A finite sum that overflows is NaN by the same rule, as in the
 // numpy twin.
 #include "nb_common.h"
+#include "nb_lds_copy.h"
 #include "nb_poisson_term.h"
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
@@ -56,24 +57,6 @@ namespace {
 constexpr int FO_WAVES = 8;                     // wavefronts of a workgroup
 constexpr int FO_RT = NB_FOLD_PANEL / FO_WAVES; // row tiles per wavefront
 static_assert(FO_RT == 2, "row tiles w and 8 + w");
-
-typedef const void __attribute__((address_space(1))) * fo_gptr;
-typedef void __attribute__((address_space(3))) * fo_lptr;
-
-// s_waitcnt vmcnt(0) (expcnt and lgkmcnt left at their maxima)
-__device__ __forceinline__ void fo_wait_copies() {
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-}
-
-// asynchronous global -> LDS copy of n_tiles operand tiles by the whole
-// workgroup in 1 KB pieces (destination = uniform base + lane * 16)
-__device__ __forceinline__ void fo_copy(const nb_gd* __restrict__ src,
-                                        double* dst, int n_tiles, int wave,
-                                        int lane) {
-  for (int c = wave; c < 2 * n_tiles; c += FO_WAVES)
-    __builtin_amdgcn_global_load_lds((fo_gptr)(src + c * 128 + 2 * lane),
-                                     (fo_lptr)(dst + c * 128), 16, 0, 0);
-}
 
 // blob: k, 1 / k, e, b, each padded to 16 DT doubles (nb_fold_r_offset), then
 // for every panel p and k-tile kt the panel's row tiles as 16x16 operand
@@ -152,7 +135,7 @@ nb_fold_poisson_kernel(const double* __restrict__ blob, int n_data, int n_src,
   // w_nxt / s_nxt.  Returns false after the last chunk.
   auto step = [&](const double* w_cur, const double* s_cur, double* w_nxt,
                   double* s_nxt) __attribute__((always_inline)) -> bool {
-    fo_wait_copies();
+    nb_wait_copies();
     __syncthreads();
     const bool last_of_panel = kt + 1 == nkt;
     const bool more = !(last_of_panel && panel + 1 == n_panels);
@@ -162,7 +145,7 @@ nb_fold_poisson_kernel(const double* __restrict__ blob, int n_data, int n_src,
     const int nrt_n = left < NB_FOLD_PANEL ? left : NB_FOLD_PANEL;
     const nb_gd* wsrc_n = wsrc + (size_t)nrt * NB_TILE;
     if (more) {
-      fo_copy(wsrc_n, w_nxt, nrt_n, wave, lane);
+      nb_copy_tiles<FO_WAVES>(wsrc_n, w_nxt, nrt_n, wave, lane);
       if (stager) load_s(kt_n);
     }
 
@@ -237,7 +220,7 @@ nb_fold_poisson_kernel(const double* __restrict__ blob, int n_data, int n_src,
   };
 
   // chunk (0, 0) into the a buffers
-  fo_copy(wsrc, w_a, nrt, wave, lane);
+  nb_copy_tiles<FO_WAVES>(wsrc, w_a, nrt, wave, lane);
   if (stager) {
     load_s(0);
     write_s(s_a, 0);

@@ -49,7 +49,7 @@ def _f64(a):
 
 
 def _dp(a):
-    return a.ctypes.data_as(_lib.c_double_p)
+    return None if a is None else a.ctypes.data_as(_lib.c_double_p)
 
 
 def as_device_points(x, n_dim=None):
@@ -537,16 +537,71 @@ def prior_transform(u, kind, loc, scale):
 ROW_MAJOR, COLUMN_MAJOR = 0, 1          # NB_PRIOR_* of include/nautilus_hip.h
 
 
-class PriorTable:
+def _shape_p(a, p, name):
+    """``a`` as a float64 array of shape (p,); None stays None."""
+    if a is None:
+        return None
+    a = _f64(a)
+    if a.shape != (p,):
+        raise ValueError('%s must have shape (%d,)' % (name, p))
+    return a
+
+
+def _data_vector(a, name):
+    a = _f64(a)
+    if a.ndim != 1:
+        raise ValueError('%s must be one-dimensional' % name)
+    return a
+
+
+class _Table:
+    """A handle of the library that lives as long as the object: ``_create``
+    makes it, ``__del__`` hands it to the library's ``_destroy``."""
+
+    _destroy = None
+
+    def _create(self, create, *args):
+        self._lib = _lib.load()
+        h = C.c_void_p()
+        _lib.check(getattr(self._lib, create)(*args, C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, '_h', None)
+        if h:
+            getattr(self._lib, self._destroy)(h)
+            self._h = None
+
+    def _rows_loglike(self, fn, *batches, head=()):
+        """fn(handle, *head, pointer and row stride of every batch, n, out,
+        stream).  A batch is (rows, width, ld): a cuda float64 tensor read in
+        place, whose rows may be strided (``stride(1) == 1``, ``stride(0) >=
+        width``); ``ld`` overrides the row stride (in doubles) it reports."""
+        first = batches[0][0]
+        n = first.shape[0]
+        args = []
+        for rows, width, ld in batches:
+            if ld is None:
+                ld = rows.stride(0) if n > 1 else width
+            args += [_ptr(rows), ld]
+        out = torch.empty(n, dtype=torch.float64, device=first.device)
+        # the C order of every *_loglike: handle, [mode,] (rows, ld) per
+        # batch, n, out, stream
+        _lib.check(fn(self._h, *head, *args, n, _ptr(out), _stream()))
+        return out
+
+
+class PriorTable(_Table):
     """Device-resident table of a prior (``nb_prior_table_create``): kind,
     loc, scale and two shapes per free parameter, and for every key of the
     prior the column it shows (its own, or its root's for a tied parameter)
     or -1 with the constant of a fixed parameter.  Uploaded once; every
     ``transform`` is one launch on the current stream."""
 
+    _destroy = 'nb_prior_table_destroy'
+
     def __init__(self, kind, loc, scale, shape0, shape1, key_column,
                  key_value):
-        self._lib = lib = _lib.load()
         kind = np.ascontiguousarray(kind, dtype=np.uint8)
         arrays = [_f64(a) for a in (loc, scale, shape0, shape1)]
         key_column = np.ascontiguousarray(key_column, dtype=np.int32)
@@ -555,19 +610,11 @@ class PriorTable:
         if any(len(a) != self.n_dim for a in arrays) or \
                 len(key_value) != self.n_keys:
             raise ValueError('prior table arrays differ in length')
-        h = C.c_void_p()
-        _lib.check(lib.nb_prior_table_create(
-            self.n_dim, kind.ctypes.data_as(C.c_void_p),
-            *[_dp(a) for a in arrays], self.n_keys,
-            key_column.ctypes.data_as(_lib.c_int32_p), _dp(key_value),
-            C.byref(h)))
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, '_h', None)
-        if h:
-            self._lib.nb_prior_table_destroy(h)
-            self._h = None
+        self._create(
+            'nb_prior_table_create', self.n_dim,
+            kind.ctypes.data_as(C.c_void_p), *[_dp(a) for a in arrays],
+            self.n_keys, key_column.ctypes.data_as(_lib.c_int32_p),
+            _dp(key_value))
 
     def transform(self, u, layout=ROW_MAJOR):
         """x = dist.isf(1 - u) (reference prior.py:85-120) of the rows of a
@@ -582,15 +629,16 @@ class PriorTable:
         return out
 
 
-class MixtureTable:
+class MixtureTable(_Table):
     """Device-resident components of a Gaussian mixture
     (``nb_mixture_create``): means (K, D), the lower-triangular inverse
     Cholesky factors ``chol_inv`` (K, D, D) and ``log_coef`` (K,) = log w_k -
     D/2 log 2 pi - sum log diag L_k.  Packed and uploaded once; every
     ``loglike`` is one launch on the current stream."""
 
+    _destroy = 'nb_mixture_destroy'
+
     def __init__(self, means, chol_inv, log_coef):
-        self._lib = lib = _lib.load()
         means = _f64(means)
         chol_inv = _f64(chol_inv)
         log_coef = _f64(log_coef)
@@ -598,17 +646,8 @@ class MixtureTable:
                 or log_coef.shape != means.shape[:1]:
             raise ValueError('mixture arrays differ in shape')
         self.n_components, self.n_dim = means.shape
-        h = C.c_void_p()
-        _lib.check(lib.nb_mixture_create(
-            self.n_dim, self.n_components, _dp(means), _dp(chol_inv),
-            _dp(log_coef), C.byref(h)))
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, '_h', None)
-        if h:
-            self._lib.nb_mixture_destroy(h)
-            self._h = None
+        self._create('nb_mixture_create', self.n_dim, self.n_components,
+                     _dp(means), _dp(chol_inv), _dp(log_coef))
 
     def loglike(self, x, labels=False):
         """log L of the rows of ``x`` as a cuda tensor; with ``labels`` also
@@ -624,102 +663,57 @@ class MixtureTable:
         return (out, lab) if labels else out
 
 
-class Chi2Table:
+class Chi2Table(_Table):
     """Device-resident data vector of a Gaussian likelihood
     (``nb_chi2_create``): ``data`` (P,) and either the lower-triangular
     inverse Cholesky factor ``chol_inv`` (P, P) of the covariance or
     ``inv_sigma`` (P,) = 1 / sigma of a diagonal one.  Packed and uploaded
     once; every ``loglike`` is one launch on the current stream."""
 
+    _destroy = 'nb_chi2_destroy'
+
     def __init__(self, data, chol_inv=None, inv_sigma=None, log_norm=0.0):
-        self._lib = lib = _lib.load()
-        data = _f64(data)
-        if data.ndim != 1:
-            raise ValueError('data must be one-dimensional')
+        data = _data_vector(data, 'data')
         self.n_data = p = len(data)
         if chol_inv is not None:
             chol_inv = _f64(chol_inv)
             if chol_inv.shape != (p, p):
                 raise ValueError('chol_inv must have shape (%d, %d)' % (p, p))
-        if inv_sigma is not None:
-            inv_sigma = _f64(inv_sigma)
-            if inv_sigma.shape != (p,):
-                raise ValueError('inv_sigma must have shape (%d,)' % p)
-        h = C.c_void_p()
-        _lib.check(lib.nb_chi2_create(
-            p, _dp(data), None if chol_inv is None else _dp(chol_inv),
-            None if inv_sigma is None else _dp(inv_sigma), float(log_norm),
-            C.byref(h)))
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, '_h', None)
-        if h:
-            self._lib.nb_chi2_destroy(h)
-            self._h = None
+        inv_sigma = _shape_p(inv_sigma, p, 'inv_sigma')
+        self._create('nb_chi2_create', p, _dp(data), _dp(chol_inv),
+                     _dp(inv_sigma), float(log_norm))
 
     def loglike(self, model, ld=None):
         """log L of the rows of the cuda float64 tensor ``model`` (n, P),
-        read in place: its rows may be strided (``stride(1) == 1``,
-        ``stride(0) >= P``).  ``ld`` overrides the row stride (in doubles)
-        the tensor reports."""
-        n = model.shape[0]
-        if ld is None:
-            ld = model.stride(0) if n > 1 else self.n_data
-        out = torch.empty(n, dtype=torch.float64, device=model.device)
-        _lib.check(self._lib.nb_chi2_loglike(
-            self._h, _ptr(model), ld, n, _ptr(out), _stream()))
-        return out
+        read in place (``_rows_loglike``)."""
+        return self._rows_loglike(self._lib.nb_chi2_loglike,
+                                  (model, self.n_data, ld))
 
 
-class PoissonTable:
+class PoissonTable(_Table):
     """Device-resident bins of a Poisson likelihood (``nb_poisson_create``):
     ``counts`` (P,) >= 0, ``exposure`` (P,) > 0 (None = 1) and ``background``
     (P,) >= 0 (None = 0), with ``log_const`` added to every result.  Uploaded
     once; every ``loglike`` is one launch on the current stream."""
 
-    def __init__(self, counts, exposure=None, background=None, log_const=0.0):
-        self._lib = lib = _lib.load()
-        counts = _f64(counts)
-        if counts.ndim != 1:
-            raise ValueError('counts must be one-dimensional')
-        self.n_data = p = len(counts)
-        if exposure is not None:
-            exposure = _f64(exposure)
-            if exposure.shape != (p,):
-                raise ValueError('exposure must have shape (%d,)' % p)
-        if background is not None:
-            background = _f64(background)
-            if background.shape != (p,):
-                raise ValueError('background must have shape (%d,)' % p)
-        h = C.c_void_p()
-        _lib.check(lib.nb_poisson_create(
-            p, _dp(counts), None if exposure is None else _dp(exposure),
-            None if background is None else _dp(background),
-            float(log_const), C.byref(h)))
-        self._h = h
+    _destroy = 'nb_poisson_destroy'
 
-    def __del__(self):
-        h = getattr(self, '_h', None)
-        if h:
-            self._lib.nb_poisson_destroy(h)
-            self._h = None
+    def __init__(self, counts, exposure=None, background=None, log_const=0.0):
+        counts = _data_vector(counts, 'counts')
+        self.n_data = p = len(counts)
+        exposure = _shape_p(exposure, p, 'exposure')
+        background = _shape_p(background, p, 'background')
+        self._create('nb_poisson_create', p, _dp(counts), _dp(exposure),
+                     _dp(background), float(log_const))
 
     def loglike(self, model, ld=None):
         """log L of the rows of the cuda float64 tensor ``model`` (n, P),
-        read in place: its rows may be strided (``stride(1) == 1``,
-        ``stride(0) >= P``).  ``ld`` overrides the row stride (in doubles)
-        the tensor reports."""
-        n = model.shape[0]
-        if ld is None:
-            ld = model.stride(0) if n > 1 else self.n_data
-        out = torch.empty(n, dtype=torch.float64, device=model.device)
-        _lib.check(self._lib.nb_poisson_loglike(
-            self._h, _ptr(model), ld, n, _ptr(out), _stream()))
-        return out
+        read in place (``_rows_loglike``)."""
+        return self._rows_loglike(self._lib.nb_poisson_loglike,
+                                  (model, self.n_data, ld))
 
 
-class FoldedPoissonTable:
+class FoldedPoissonTable(_Table):
     """Device-resident bins and response matrix of a Poisson likelihood whose
     model lives in a source space (``nb_fold_poisson_create``): ``counts``,
     ``exposure``, ``background`` and ``log_const`` as in ``PoissonTable``,
@@ -727,51 +721,27 @@ class FoldedPoissonTable:
     Packed and uploaded once; every ``loglike`` is one launch on the current
     stream that never stores the (n, P) expected counts."""
 
+    _destroy = 'nb_fold_poisson_destroy'
+
     def __init__(self, counts, response, exposure=None, background=None,
                  log_const=0.0):
-        self._lib = lib = _lib.load()
-        counts = _f64(counts)
-        if counts.ndim != 1:
-            raise ValueError('counts must be one-dimensional')
+        counts = _data_vector(counts, 'counts')
         self.n_data = p = len(counts)
         response = _f64(response)
         if response.ndim != 2 or response.shape[0] != p:
             raise ValueError('response must have shape (%d, K)' % p)
         self.n_source = k = response.shape[1]
-        if exposure is not None:
-            exposure = _f64(exposure)
-            if exposure.shape != (p,):
-                raise ValueError('exposure must have shape (%d,)' % p)
-        if background is not None:
-            background = _f64(background)
-            if background.shape != (p,):
-                raise ValueError('background must have shape (%d,)' % p)
-        h = C.c_void_p()
-        _lib.check(lib.nb_fold_poisson_create(
-            p, k, _dp(counts), _dp(response), k,
-            None if exposure is None else _dp(exposure),
-            None if background is None else _dp(background),
-            float(log_const), C.byref(h)))
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, '_h', None)
-        if h:
-            self._lib.nb_fold_poisson_destroy(h)
-            self._h = None
+        exposure = _shape_p(exposure, p, 'exposure')
+        background = _shape_p(background, p, 'background')
+        self._create('nb_fold_poisson_create', p, k, _dp(counts),
+                     _dp(response), k, _dp(exposure), _dp(background),
+                     float(log_const))
 
     def loglike(self, src, ld=None):
         """log L of the rows of the cuda float64 tensor ``src`` (n, K), read
-        in place: its rows may be strided (``stride(1) == 1``,
-        ``stride(0) >= K``).  ``ld`` overrides the row stride (in doubles)
-        the tensor reports."""
-        n = src.shape[0]
-        if ld is None:
-            ld = src.stride(0) if n > 1 else self.n_source
-        out = torch.empty(n, dtype=torch.float64, device=src.device)
-        _lib.check(self._lib.nb_fold_poisson_loglike(
-            self._h, _ptr(src), ld, n, _ptr(out), _stream()))
-        return out
+        in place (``_rows_loglike``)."""
+        return self._rows_loglike(self._lib.nb_fold_poisson_loglike,
+                                  (src, self.n_source, ld))
 
 
 NOISE_ROW, NOISE_FULL = 0, 1       # NB_NOISE_ROW, NB_NOISE_FULL
@@ -789,54 +759,33 @@ def noise_launch_shape(n_data):
     return 64, 1, 4
 
 
-class NoiseTable:
+class NoiseTable(_Table):
     """Device-resident measurements of a Gaussian likelihood whose variance
     depends on the point (``nb_noise_create``): ``data`` (P,) finite and
     ``sigma2`` (P,) = sigma^2 >= 0 (None = 0), with ``log_norm`` added to
     every result.  Uploaded once; every ``loglike`` is one launch on the
     current stream."""
 
-    def __init__(self, data, sigma2=None, log_norm=0.0):
-        self._lib = lib = _lib.load()
-        data = _f64(data)
-        if data.ndim != 1:
-            raise ValueError('data must be one-dimensional')
-        self.n_data = p = len(data)
-        if sigma2 is not None:
-            sigma2 = _f64(sigma2)
-            if sigma2.shape != (p,):
-                raise ValueError('sigma2 must have shape (%d,)' % p)
-        h = C.c_void_p()
-        _lib.check(lib.nb_noise_create(
-            p, _dp(data), None if sigma2 is None else _dp(sigma2),
-            float(log_norm), C.byref(h)))
-        self._h = h
+    _destroy = 'nb_noise_destroy'
 
-    def __del__(self):
-        h = getattr(self, '_h', None)
-        if h:
-            self._lib.nb_noise_destroy(h)
-            self._h = None
+    def __init__(self, data, sigma2=None, log_norm=0.0):
+        data = _data_vector(data, 'data')
+        self.n_data = p = len(data)
+        sigma2 = _shape_p(sigma2, p, 'sigma2')
+        self._create('nb_noise_create', p, _dp(data), _dp(sigma2),
+                     float(log_norm))
 
     def loglike(self, model, noise, mode, ld=None, ld_noise=None):
         """log L of the rows of the cuda float64 tensors ``model`` (n, P) and
         ``noise`` ((n, 3) with ``mode`` NOISE_ROW, (n, P) with NOISE_FULL),
-        both read in place: their rows may be strided (``stride(1) == 1``,
-        ``stride(0)`` at least the width).  ``ld`` and ``ld_noise`` override
-        the row strides (in doubles) the tensors report."""
+        both read in place (``_rows_loglike``)."""
         n = model.shape[0]
         if noise.shape[0] != n:
             raise ValueError('model and noise must have the same number of '
                              'rows, not %d and %d' % (n, noise.shape[0]))
-        if ld is None:
-            ld = model.stride(0) if n > 1 else self.n_data
-        if ld_noise is None:
-            ld_noise = noise.stride(0) if n > 1 else noise.shape[1]
-        out = torch.empty(n, dtype=torch.float64, device=model.device)
-        _lib.check(self._lib.nb_noise_loglike(
-            self._h, mode, _ptr(model), ld, _ptr(noise), ld_noise, n,
-            _ptr(out), _stream()))
-        return out
+        return self._rows_loglike(
+            self._lib.nb_noise_loglike, (model, self.n_data, ld),
+            (noise, noise.shape[1], ld_noise), head=(mode,))
 
 
 def gmm_fit(x, n_init=10, seed=0, tol=1e-3, reg_covar=1e-6, max_iter=100,

@@ -67,7 +67,120 @@ class GaussianLikelihood:
         return state
 
 
-class GaussianMixtureLikelihood:
+class _DeviceTables:
+    """The device handles of a likelihood, one per device, built on first use
+    by the subclass's ``_make_table`` and left behind when it is pickled."""
+
+    def _table(self):
+        """The device handle of the current device, built on first use."""
+        dev = torch.cuda.current_device()
+        if dev not in self._tables:
+            self._tables[dev] = self._make_table()
+        return self._tables[dev]
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        if '_tables' in state:
+            state['_tables'] = {}
+        return state
+
+
+def _numbers(a, p, name, positive):
+    """``a`` as P finite numbers that are positive / not negative."""
+    a = np.asarray(a, float)
+    if a.shape != (p,) or not np.all(np.isfinite(a)) or \
+            not np.all(a > 0 if positive else a >= 0):
+        raise ValueError('%s must be %d %s' % (
+            name, p, 'positive finite numbers' if positive
+            else 'finite numbers that are not negative'))
+    return a
+
+
+def _bounded_vector(a, name, n_max, unit):
+    """``a`` as a vector of 1 to ``n_max`` numbers."""
+    a = np.asarray(a, float)
+    if a.ndim != 1 or len(a) < 1:
+        raise ValueError('%s must be a vector of at least one number' % name)
+    if len(a) > n_max:
+        raise ValueError('at most %d %s are supported, not %d' %
+                         (n_max, unit, len(a)))
+    return a
+
+
+class _ModelLikelihood(_DeviceTables):
+    """A likelihood that runs the user's ``model`` on the batch and then one
+    fused kernel on what it returns.  A subclass says how wide the rows of
+    every output are (``_widths``), makes its table (``_make_table``) and has
+    the pure-numpy ``numpy_from_model``; ``_pair`` is set where the model
+    returns a pair of outputs and ``_what`` names them in messages."""
+
+    device = True
+    _pair = False
+    _what = 'the model output'
+
+    def __init__(self, model):
+        if not callable(model):
+            raise ValueError('model must be callable')
+        self.model = model
+        self._tables = {}
+
+    def _check(self, m):
+        p = self._widths()[0]
+        if m.ndim != 2 or m.shape[1] != p:
+            raise ValueError('the model output must have shape (n, %d), not '
+                             '%s' % (p, tuple(m.shape)))
+
+    @staticmethod
+    def _rows(t, width):
+        """``t`` on the device, as it is where its rows can be read in place
+        and contiguous otherwise."""
+        t = t if t.is_cuda else t.cuda()
+        in_place = (width == 1 or t.stride(1) == 1) and \
+            (t.shape[0] <= 1 or t.stride(0) >= width)
+        return t if in_place else t.contiguous()
+
+    def _loglike(self, *rows):
+        return self._table().loglike(*rows)
+
+    def _from_outputs(self, *outputs):
+        """``from_model``: float64 cuda tensors in, a cuda tensor out; numpy
+        in, numpy out."""
+        tensors = isinstance(outputs[0], torch.Tensor)
+        if not tensors:
+            outputs = [np.asarray(t) for t in outputs]
+        for t in outputs:
+            if t.dtype != (torch.float64 if tensors else np.float64):
+                raise ValueError('%s must be float64, not %s' %
+                                 (self._what, t.dtype))
+        self._check(*outputs)
+        if tensors:
+            return self._loglike(*[self._rows(t, width) for t, width in
+                                   zip(outputs, self._widths())])
+        return self._from_outputs(*[
+            torch.from_numpy(np.ascontiguousarray(t)).cuda()
+            for t in outputs]).cpu().numpy()
+
+    def _outputs(self, x):
+        if self._pair:
+            m, w = self.model(x)       # anything but a pair fails to unpack
+            return m, w
+        return (self.model(x),)
+
+    def __call__(self, x):
+        if isinstance(x, torch.Tensor):
+            return self.from_model(*self._outputs(x))
+        xs = device.as_device_points(x)
+        return self.from_model(*self._outputs(xs)).cpu().numpy()
+
+    def numpy(self, x):
+        """Pure-numpy twin of a call: the model runs on the CPU."""
+        x = np.atleast_2d(np.asarray(x, float))
+        return self.numpy_from_model(*[
+            t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t
+            for t in self._outputs(torch.from_numpy(x))])
+
+
+class GaussianMixtureLikelihood(_DeviceTables):
     """Mixture of Gaussians  log sum_k w_k N(x; mu_k, Sigma_k).
 
     ``GaussianMixtureLikelihood(means, sigma)`` is the equal-weight isotropic
@@ -115,10 +228,7 @@ class GaussianMixtureLikelihood:
         self.covs = covs.copy()
         if weights is None:
             weights = np.full(k, 1.0)
-        weights = np.asarray(weights, float)
-        if weights.shape != (k,) or not np.all(np.isfinite(weights)) or \
-                not np.all(weights > 0):
-            raise ValueError('weights must be %d positive finite numbers' % k)
+        weights = _numbers(weights, k, 'weights', True)
         self.weights = weights / np.sum(weights)
         self._chol = np.empty((k, d, d))
         for i in range(k):
@@ -134,18 +244,12 @@ class GaussianMixtureLikelihood:
                                                     axis2=2)), axis=1))
         self._tables = {}
 
-    def _table(self):
-        """The device handle of the current device, built on first use."""
-        dev = torch.cuda.current_device()
-        if dev not in self._tables:
-            from scipy.linalg import solve_triangular
-            eye = np.eye(self.n_dim)
-            chol_inv = np.stack([
-                np.tril(solve_triangular(c, eye, lower=True))
-                for c in self._chol])
-            self._tables[dev] = device.MixtureTable(self.means, chol_inv,
-                                                    self._log_coef)
-        return self._tables[dev]
+    def _make_table(self):
+        from scipy.linalg import solve_triangular
+        eye = np.eye(self.n_dim)
+        chol_inv = np.stack([np.tril(solve_triangular(c, eye, lower=True))
+                             for c in self._chol])
+        return device.MixtureTable(self.means, chol_inv, self._log_coef)
 
     def __call__(self, x):
         if not self.fused:
@@ -187,17 +291,11 @@ class GaussianMixtureLikelihood:
             terms[i] = self._log_coef[i] - 0.5 * np.sum(y**2, axis=0)
         return terms
 
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        if '_tables' in state:
-            state['_tables'] = {}
-        return state
-
 
 N_DATA_MAX = 4096                  # NB_CHI2_MAX_DATA of include/nautilus_hip.h
 
 
-class GaussianDataLikelihood:
+class GaussianDataLikelihood(_ModelLikelihood):
     """Gaussian likelihood of a data vector:  log L(theta) = log_norm -
     1/2 (m(theta) - d)^T C^-1 (m(theta) - d).
 
@@ -219,18 +317,9 @@ class GaussianDataLikelihood:
     A non-finite entry in row i of the model output makes ``out[i]`` NaN and
     changes no bit of any other row."""
 
-    device = True
-
     def __init__(self, model, data, *, cov=None, sigma=None, normalised=True):
-        if not callable(model):
-            raise ValueError('model must be callable')
-        self.model = model
-        data = np.asarray(data, float)
-        if data.ndim != 1 or len(data) < 1:
-            raise ValueError('data must be a vector of at least one number')
-        if len(data) > N_DATA_MAX:
-            raise ValueError('at most %d data points are supported, not %d' %
-                             (N_DATA_MAX, len(data)))
+        super().__init__(model)
+        data = _bounded_vector(data, 'data', N_DATA_MAX, 'data points')
         if not np.all(np.isfinite(data)):
             raise ValueError('data must be finite')
         if (cov is None) == (sigma is None):
@@ -239,11 +328,7 @@ class GaussianDataLikelihood:
         self.n_data = p = len(data)
         self.cov = self.sigma = self._chol = None
         if sigma is not None:
-            sigma = np.asarray(sigma, float)
-            if sigma.shape != (p,) or not np.all(np.isfinite(sigma)) or \
-                    not np.all(sigma > 0):
-                raise ValueError('sigma must be %d positive finite numbers'
-                                 % p)
+            sigma = _numbers(sigma, p, 'sigma', True)
             self.sigma = sigma.copy()
             log_det = 2.0 * np.sum(np.log(sigma))
         else:
@@ -264,55 +349,24 @@ class GaussianDataLikelihood:
             log_det = 2.0 * np.sum(np.log(np.diag(self._chol)))
         self.log_norm = (-0.5 * (p * np.log(2 * np.pi) + log_det)
                          if normalised else 0.0)
-        self._tables = {}
 
-    def _table(self):
-        """The device handle of the current device, built on first use."""
-        dev = torch.cuda.current_device()
-        if dev not in self._tables:
-            if self.sigma is not None:
-                table = device.Chi2Table(self.data, inv_sigma=1.0 / self.sigma,
-                                         log_norm=self.log_norm)
-            else:
-                from scipy.linalg import solve_triangular
-                chol_inv = np.tril(solve_triangular(
-                    self._chol, np.eye(self.n_data), lower=True))
-                table = device.Chi2Table(self.data, chol_inv=chol_inv,
-                                         log_norm=self.log_norm)
-            self._tables[dev] = table
-        return self._tables[dev]
+    def _make_table(self):
+        if self.sigma is not None:
+            return device.Chi2Table(self.data, inv_sigma=1.0 / self.sigma,
+                                    log_norm=self.log_norm)
+        from scipy.linalg import solve_triangular
+        chol_inv = np.tril(solve_triangular(
+            self._chol, np.eye(self.n_data), lower=True))
+        return device.Chi2Table(self.data, chol_inv=chol_inv,
+                                log_norm=self.log_norm)
 
-    def _check(self, m):
-        if m.ndim != 2 or m.shape[1] != self.n_data:
-            raise ValueError('the model output must have shape (n, %d), not '
-                             '%s' % (self.n_data, tuple(m.shape)))
+    def _widths(self):
+        return (self.n_data,)
 
     def from_model(self, m):
         """log L of the rows of an (n, P) float64 model output: a cuda tensor
         in, a cuda tensor out; numpy in, numpy out."""
-        if isinstance(m, torch.Tensor):
-            if m.dtype != torch.float64:
-                raise ValueError('the model output must be float64, not %s' %
-                                 m.dtype)
-            self._check(m)
-            t = m if m.is_cuda else m.cuda()
-            p = self.n_data
-            in_place = (p == 1 or t.stride(1) == 1) and \
-                (t.shape[0] <= 1 or t.stride(0) >= p)
-            return self._table().loglike(t if in_place else t.contiguous())
-        m = np.asarray(m)
-        if m.dtype != np.float64:
-            raise ValueError('the model output must be float64, not %s' %
-                             m.dtype)
-        self._check(m)
-        t = torch.from_numpy(np.ascontiguousarray(m)).cuda()
-        return self._table().loglike(t).cpu().numpy()
-
-    def __call__(self, x):
-        if isinstance(x, torch.Tensor):
-            return self.from_model(self.model(x))
-        xs = device.as_device_points(x)
-        return self.from_model(self.model(xs)).cpu().numpy()
+        return self._from_outputs(m)
 
     def numpy_from_model(self, m):
         """Pure-numpy evaluation of an (n, P) model output (CPU baseline /
@@ -330,19 +384,6 @@ class GaussianDataLikelihood:
         out = self.log_norm - 0.5 * np.sum(y**2, axis=1)
         out[~np.all(np.isfinite(r), axis=1)] = np.nan
         return out
-
-    def numpy(self, x):
-        """Pure-numpy twin of a call: the model runs on the CPU."""
-        x = np.atleast_2d(np.asarray(x, float))
-        m = self.model(torch.from_numpy(x))
-        if isinstance(m, torch.Tensor):
-            m = m.detach().cpu().numpy()
-        return self.numpy_from_model(m)
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state['_tables'] = {}
-        return state
 
 
 N_COUNTS_MAX = 1 << 20             # NB_POISSON_MAX_DATA of nautilus_hip.h
@@ -393,7 +434,7 @@ def poisson_log_const(counts):
     return out
 
 
-class PoissonDataLikelihood:
+class PoissonDataLikelihood(_ModelLikelihood):
     """Poisson likelihood of counts in bins:  log L(theta) = sum_j log
     Poisson(k_j | mu_j(theta)),  mu_j = exposure_j m_j(theta) + background_j.
 
@@ -441,19 +482,10 @@ class PoissonDataLikelihood:
     twins fold with ``s @ R.T`` first.  A NaN or infinite source value makes
     its row NaN, also where the column of R it meets is all zeros."""
 
-    device = True
-
     def __init__(self, model, counts, *, exposure=None, background=None,
                  normalised=True, response=None):
-        if not callable(model):
-            raise ValueError('model must be callable')
-        self.model = model
-        counts = np.asarray(counts, float)
-        if counts.ndim != 1 or len(counts) < 1:
-            raise ValueError('counts must be a vector of at least one number')
-        if len(counts) > N_COUNTS_MAX:
-            raise ValueError('at most %d bins are supported, not %d' %
-                             (N_COUNTS_MAX, len(counts)))
+        super().__init__(model)
+        counts = _bounded_vector(counts, 'counts', N_COUNTS_MAX, 'bins')
         if not np.all(np.isfinite(counts)) or not np.all(counts >= 0):
             raise ValueError('counts must be finite and not negative')
         with np.errstate(divide='ignore', over='ignore'):
@@ -465,23 +497,12 @@ class PoissonDataLikelihood:
         if exposure is None:
             self.exposure = np.ones(p)
         else:
-            exposure = np.asarray(exposure, float)
-            if exposure.shape != (p,) or \
-                    not np.all(np.isfinite(exposure)) or \
-                    not np.all(exposure > 0):
-                raise ValueError('exposure must be %d positive finite numbers'
-                                 % p)
-            self.exposure = exposure.copy()
+            self.exposure = _numbers(exposure, p, 'exposure', True).copy()
         if background is None:
             self.background = np.zeros(p)
         else:
-            background = np.asarray(background, float)
-            if background.shape != (p,) or \
-                    not np.all(np.isfinite(background)) or \
-                    not np.all(background >= 0):
-                raise ValueError('background must be %d finite numbers that '
-                                 'are not negative' % p)
-            self.background = background.copy()
+            self.background = _numbers(background, p, 'background',
+                                       False).copy()
         if response is None:
             self.response = None
             self.n_source = p
@@ -510,54 +531,24 @@ class PoissonDataLikelihood:
                           if normalised else 0.0)
         if not np.isfinite(self.log_const):
             raise ValueError('counts are too large: log_const is not finite')
-        self._tables = {}
 
-    def _table(self):
-        """The device handle of the current device, built on first use."""
-        dev = torch.cuda.current_device()
-        if dev not in self._tables:
-            if self.response is None:
-                self._tables[dev] = device.PoissonTable(
-                    self.counts, self.exposure, self.background,
-                    log_const=self.log_const)
-            else:
-                self._tables[dev] = device.FoldedPoissonTable(
-                    self.counts, self.response, self.exposure,
-                    self.background, log_const=self.log_const)
-        return self._tables[dev]
+    def _make_table(self):
+        if self.response is None:
+            return device.PoissonTable(
+                self.counts, self.exposure, self.background,
+                log_const=self.log_const)
+        return device.FoldedPoissonTable(
+            self.counts, self.response, self.exposure, self.background,
+            log_const=self.log_const)
 
-    def _check(self, m):
-        if m.ndim != 2 or m.shape[1] != self.n_source:
-            raise ValueError('the model output must have shape (n, %d), not '
-                             '%s' % (self.n_source, tuple(m.shape)))
+    def _widths(self):
+        return (self.n_source,)
 
     def from_model(self, m):
         """log L of the rows of an (n, P) float64 model output ((n, K) with a
         response): a cuda tensor in, a cuda tensor out; numpy in, numpy
         out."""
-        if isinstance(m, torch.Tensor):
-            if m.dtype != torch.float64:
-                raise ValueError('the model output must be float64, not %s' %
-                                 m.dtype)
-            self._check(m)
-            t = m if m.is_cuda else m.cuda()
-            p = self.n_source
-            in_place = (p == 1 or t.stride(1) == 1) and \
-                (t.shape[0] <= 1 or t.stride(0) >= p)
-            return self._table().loglike(t if in_place else t.contiguous())
-        m = np.asarray(m)
-        if m.dtype != np.float64:
-            raise ValueError('the model output must be float64, not %s' %
-                             m.dtype)
-        self._check(m)
-        t = torch.from_numpy(np.ascontiguousarray(m)).cuda()
-        return self._table().loglike(t).cpu().numpy()
-
-    def __call__(self, x):
-        if isinstance(x, torch.Tensor):
-            return self.from_model(self.model(x))
-        xs = device.as_device_points(x)
-        return self.from_model(self.model(xs)).cpu().numpy()
+        return self._from_outputs(m)
 
     def numpy_deviance(self, m):
         """The (n, P) terms D(mu_ij, k_j) of an (n, P) model output ((n, K)
@@ -593,24 +584,11 @@ class PoissonDataLikelihood:
         out[np.any(np.isnan(d), axis=1)] = np.nan
         return out
 
-    def numpy(self, x):
-        """Pure-numpy twin of a call: the model runs on the CPU."""
-        x = np.atleast_2d(np.asarray(x, float))
-        m = self.model(torch.from_numpy(x))
-        if isinstance(m, torch.Tensor):
-            m = m.detach().cpu().numpy()
-        return self.numpy_from_model(m)
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state['_tables'] = {}
-        return state
-
 
 N_NOISE_MAX = 1 << 20              # NB_NOISE_MAX_DATA of nautilus_hip.h
 
 
-class GaussianNoiseLikelihood:
+class GaussianNoiseLikelihood(_ModelLikelihood):
     """Gaussian likelihood of independent measurements whose error bars carry
     free parameters:
 
@@ -647,23 +625,17 @@ class GaussianNoiseLikelihood:
     changes no bit of any other row.  The signs of the single coefficients do
     not matter as long as v > 0."""
 
-    device = True
+    _pair = True
+    _what = 'the model output and the noise'
 
     def __init__(self, model, data, sigma=None, *, noise='row',
                  normalised=True):
-        if not callable(model):
-            raise ValueError('model must be callable')
-        self.model = model
+        super().__init__(model)
         if noise not in ('row', 'full'):
             raise ValueError("noise must be 'row' or 'full', not %r" %
                              (noise,))
         self.noise = noise
-        data = np.asarray(data, float)
-        if data.ndim != 1 or len(data) < 1:
-            raise ValueError('data must be a vector of at least one number')
-        if len(data) > N_NOISE_MAX:
-            raise ValueError('at most %d data points are supported, not %d' %
-                             (N_NOISE_MAX, len(data)))
+        data = _bounded_vector(data, 'data', N_NOISE_MAX, 'data points')
         if not np.all(np.isfinite(data)):
             raise ValueError('data must be finite')
         self.data = data.copy()
@@ -671,81 +643,43 @@ class GaussianNoiseLikelihood:
         if sigma is None:
             self.sigma = np.zeros(p)
         else:
-            sigma = np.asarray(sigma, float)
-            if sigma.shape != (p,) or not np.all(np.isfinite(sigma)) or \
-                    not np.all(sigma >= 0):
-                raise ValueError('sigma must be %d finite numbers that are '
-                                 'not negative' % p)
-            self.sigma = sigma.copy()
+            self.sigma = _numbers(sigma, p, 'sigma', False).copy()
         with np.errstate(over='ignore'):
             self._sigma2 = self.sigma * self.sigma
         if not np.all(np.isfinite(self._sigma2)):
             raise ValueError('sigma is too large: sigma^2 is not finite')
         self.log_norm = -0.5 * p * np.log(2 * np.pi) if normalised else 0.0
-        self._tables = {}
 
     @property
     def _width(self):
         return 3 if self.noise == 'row' else self.n_data
 
-    def _table(self):
-        """The device handle of the current device, built on first use."""
-        dev = torch.cuda.current_device()
-        if dev not in self._tables:
-            self._tables[dev] = device.NoiseTable(
-                self.data, self._sigma2, log_norm=self.log_norm)
-        return self._tables[dev]
+    def _make_table(self):
+        return device.NoiseTable(self.data, self._sigma2,
+                                 log_norm=self.log_norm)
+
+    def _widths(self):
+        return self.n_data, self._width
+
+    def _loglike(self, m, w):
+        return self._table().loglike(
+            m, w, device.NOISE_ROW if self.noise == 'row'
+            else device.NOISE_FULL)
 
     def _check(self, m, w):
-        if m.ndim != 2 or m.shape[1] != self.n_data:
-            raise ValueError('the model output must have shape (n, %d), not '
-                             '%s' % (self.n_data, tuple(m.shape)))
+        super()._check(m)
         if w.ndim != 2 or tuple(w.shape) != (m.shape[0], self._width):
             raise ValueError('the noise must have shape (%d, %d), not %s' %
                              (m.shape[0], self._width, tuple(w.shape)))
-
-    @staticmethod
-    def _rows(t, width):
-        """``t`` on the device, as it is where its rows can be read in place
-        and contiguous otherwise."""
-        t = t if t.is_cuda else t.cuda()
-        in_place = (width == 1 or t.stride(1) == 1) and \
-            (t.shape[0] <= 1 or t.stride(0) >= width)
-        return t if in_place else t.contiguous()
 
     def from_model(self, m, w):
         """log L of the rows of an (n, P) float64 model output and its noise
         ((n, 3) or (n, P)): cuda tensors in, a cuda tensor out; numpy in,
         numpy out."""
-        tensors = isinstance(m, torch.Tensor), isinstance(w, torch.Tensor)
-        if tensors[0] != tensors[1]:
+        if isinstance(m, torch.Tensor) != isinstance(w, torch.Tensor):
             raise ValueError('the model output and the noise must both be '
                              'torch tensors or both numpy arrays')
-        if tensors[0]:
-            for t in (m, w):
-                if t.dtype != torch.float64:
-                    raise ValueError('the model output and the noise must be '
-                                     'float64, not %s' % t.dtype)
-            self._check(m, w)
-            mode = device.NOISE_ROW if self.noise == 'row' else \
-                device.NOISE_FULL
-            return self._table().loglike(
-                self._rows(m, self.n_data), self._rows(w, self._width), mode)
-        m, w = np.asarray(m), np.asarray(w)
-        for t in (m, w):
-            if t.dtype != np.float64:
-                raise ValueError('the model output and the noise must be '
-                                 'float64, not %s' % t.dtype)
-        self._check(m, w)
-        return self.from_model(
-            torch.from_numpy(np.ascontiguousarray(m)).cuda(),
-            torch.from_numpy(np.ascontiguousarray(w)).cuda()).cpu().numpy()
-
-    def __call__(self, x):
-        if isinstance(x, torch.Tensor):
-            return self.from_model(*self.model(x))
-        xs = device.as_device_points(x)
-        return self.from_model(*self.model(xs)).cpu().numpy()
+        return self._from_outputs(m, w)
 
     def numpy_variance(self, m, w):
         """The (n, P) variances v_ij of an (n, P) model output and its noise,
@@ -781,21 +715,6 @@ class GaussianNoiseLikelihood:
                                            axis=1)
         out[np.any(bad, axis=1)] = np.nan
         return out
-
-    def numpy(self, x):
-        """Pure-numpy twin of a call: the model runs on the CPU."""
-        x = np.atleast_2d(np.asarray(x, float))
-        m, w = self.model(torch.from_numpy(x))
-        if isinstance(m, torch.Tensor):
-            m = m.detach().cpu().numpy()
-        if isinstance(w, torch.Tensor):
-            w = w.detach().cpu().numpy()
-        return self.numpy_from_model(m, w)
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state['_tables'] = {}
-        return state
 
 
 class RosenbrockLikelihood:
