@@ -4,8 +4,22 @@
 // (_fit_stochastic), :297-389 (_backprop), _stochastic_optimizers.py:255-287
 // (Adam), _base.py:187-189 (squared loss)).
 //
-// All networks of an emulator train concurrently.  Every Adam step is two
-// kernel launches on one stream (the kernel boundary is the grid-wide sync):
+// All networks of an emulator train concurrently.  An Adam step is the two
+// phases FB and G (below), in one of two forms:
+//
+//  Resident (nb_train_xcd_kernel): ONE launch per chunk of epochs.  A network
+//      has the 32 workgroups of one XCD -- one per CU; 16 where two networks
+//      share an XCD -- which separate the phases by spin barriers in that
+//      XCD's L2; workgroups without a row tile of the minibatch start a G job
+//      of the upper layers while FB still runs (g_plan, nb_train_plan.h).
+//      Taken for up to MAX_RESIDENT networks where workgroups are dealt out
+//      over the XCDs as expected (xcd_pinning_available) and every two
+//      networks find an XCD that no live trainer owns.
+//  Two launches per step (nb_train_fb_kernel, nb_train_g_kernel): the kernel
+//      boundary is the grid-wide synchronisation, at about a third of the
+//      step in dispatch and drain.  The fallback -- where the resident form
+//      is not to be had, or on request (train_switches) -- and for networks
+//      that share one training set only.
 //
 //  FB  one workgroup of four wavefronts per 16-row tile of the minibatch:
 //      forward through the four layers (the output tiles of a layer are split
@@ -35,6 +49,7 @@
 // contracts the row tiles of the minibatch in chunks of G_PAIRS per wavefront
 // (same fixed order of summation, no atomics).
 #include "nb_common.h"
+#include "nb_train_plan.h"
 #include "../../include/nautilus_hip.h"
 
 #include <cstdio>
@@ -50,9 +65,7 @@ namespace {
 
 typedef double nb_d2 __attribute__((ext_vector_type(2)));
 
-constexpr int MAXB = 208;        // minibatch rows padded to 16 (batch <= 200)
 constexpr int LD1 = 112, LD2 = 64, LD3 = 32, LD4 = 16;
-constexpr int G_ROWT = MAXB / 16;   // 16-row tiles of a minibatch
 constexpr int SMALL_BATCH = 200;    // largest batch of the compile-time layout
 static_assert(NB_TRAIN_MAX_BATCH % 16 == 0, "row tiles of the largest batch");
 // transposed copies of the weight tiles of layers 2-4 (operands of the
@@ -70,19 +83,6 @@ constexpr int WT_DOUBLES = WT4 + 1 * NB_HT3 * NB_TILE;
 // clean lines on this part -- measured: 4.6 us per step.)
 __device__ __forceinline__ double ld_xcd(const nb_gd* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Weight tiles (W: [kt][ht], contraction index c = input unit; WT: [ht][kt],
-// c = output unit) are stored so that a lane finds the operands of two
-// consecutive k-steps side by side: k-step 2 P + j of the tile row covers
-// c = 8 P + 2 lg + j (lg = lane / 16), and element (c, r) of a tile lives at
-// ((c / 8) * 64 + ((c / 2) % 4) * 16 + r) * 2 + c % 2 -- one 16-byte load per
-// lane and PAIR of k-steps, 1 KB contiguous per wavefront.  A CU's texture
-// path moves ~26 B / clk with 8-byte and ~53 B / clk with 16-byte loads per
-// lane (profiles/tools/l2_read_bench.hip), and the forward / backward phase is made of
-// waiting for exactly these operands.
-__host__ __device__ constexpr int tile_index(int c, int r) {
-  return ((c >> 3) * 64 + ((c >> 1) & 3) * 16 + r) * 2 + (c & 1);
 }
 
 // 16-byte device-scope load (buffer_load_dwordx4 ... sc1; the global-pointer
@@ -968,7 +968,6 @@ __device__ __forceinline__ double adam_lr(const TrainArgs& a, long long t_adam) 
 // what the phase costs.  One tile per job reads two column blocks per tile, a
 // 2 x 2 block one.)  The job list is built by the host (g_jobs) so that one
 // round of 32 workgroups covers a network for every n_dim.
-constexpr int G_JOB_INTS = 5;     // layer (0..3), kt0, nk, ht0, nh
 constexpr int G_MAX_TILES = 4;
 
 struct GLayer {
@@ -1319,7 +1318,6 @@ __global__ void nb_train_epoch_kernel(TrainArgs a, long long t_adam) {
 #define NB_POLL_SLEEP_FEW 1
 #endif
 constexpr int XCD_COUNT = 8;
-constexpr int XCD_SLOTS = 32;            // workgroups per network: one per CU
 // per network 512 bytes: [0] counter of the barrier behind FB (and of those
 // around the epochs), [1] error, [32] the count of reported upper stashes,
 // [64] counter of the barrier that ends a step -- the counters of different
@@ -1779,207 +1777,70 @@ nb_train_xcd_kernel(TrainArgs a, FleetData fleet, XcdMap map, SyncTable tab,
 #endif
 }
 
-void put_w(double* tiles, int ht_n, int k, int h, double v) {
-  tiles[((size_t)(k >> 4) * ht_n + (h >> 4)) * NB_TILE +
-        tile_index(k & 15, h & 15)] = v;
-}
-double get_w(const double* tiles, int ht_n, int k, int h) {
-  return tiles[((size_t)(k >> 4) * ht_n + (h >> 4)) * NB_TILE +
-               tile_index(k & 15, h & 15)];
-}
-// The job list of the forms without a schedule (two launches per step; two
-// networks per XCD): blocks of up to 2 x 2 tiles per layer, shaped so that a
-// network needs at most 32 jobs at every n_dim (two rounds of 16 workgroups).
-std::vector<int> g_jobs_rounds(int kt1) {
-  std::vector<int> jobs;
-  auto blocks = [&](int layer, int kt_n, int ht_n, int bk, int bh) {
-    for (int kt = 0; kt < kt_n; kt += bk)
-      for (int ht = 0; ht < ht_n; ht += bh) {
-        const int rec[G_JOB_INTS] = {layer, kt, kt + bk <= kt_n ? bk : 1, ht,
-                                     ht + bh <= ht_n ? bh : 1};
-        jobs.insert(jobs.end(), rec, rec + G_JOB_INTS);
-      }
-  };
-  // layer 1 (kt1 x 7 tiles): pairs along k up to 64 dimensions, 2 x 2 beyond
-  blocks(0, kt1, NB_HT1, 2, kt1 <= 4 ? 1 : 2);
-  // layer 2 (7 x 4): pairs along h, 2 x 2 where layer 1 needs the workgroups
-  blocks(1, NB_HT1, NB_HT2, kt1 >= 7 ? 2 : 1, 2);
-  blocks(2, NB_HT2, NB_HT3, 2, 2);      // layer 3 (4 x 2)
-  blocks(3, NB_HT3, 1, 2, 1);           // layer 4 (2 x 1)
-  return jobs;
-}
-
-// The jobs of the G phase (see g_job) and their schedule on the 32 workgroups
-// of a resident network.
-//
-// Jobs: blocks of nk x nh (1 or 2 each) weight tiles of one layer.  Measured
-// on the resident kernel (profiles/r04/second_session/train_phases_*.txt) a
-// job costs about 2.2 k ticks + 0.8 k per operand column block + 1.35 k per
-// tile (MFMA chains, reduction, Adam, stores).
-//
-// Schedule: the G_ROWT workgroups with a row tile run FB; the other 19 start
-// an EARLY job each -- the 38 tiles of the layers 2-4 -- G_HEAD ticks before
-// the barrier that ends FB opens, and are free for a LATE job when they are
-// through; the layer-1 tiles are all late.  Searched: the block shape of the
-// late jobs (the job that ends last is split while that shortens the phase),
-// and the number of workgroups without a row tile that are kept for a late
-// job ONLY -- the early jobs then move together, pairs of them becoming 2 x 2
-// blocks.  (n_dim 50: thirteen 2-tile late jobs on the FB workgroups, the
-// fourteenth on a workgroup of its own, sixteen 2-tile early jobs and two of
-// 3 x 1 tiles.)  G_HEAD is small: the report of the upper stash takes three
-// round trips to the L2 (store acknowledgement, counter, poll) of ~500 ticks.
-constexpr double G_HEAD = 3.0;
-static double g_cost(int nk, int nh) {
-  return 2.2 + 0.8 * (nk + nh) + 1.35 * nk * nh;
-}
-struct GRec { int layer, kt0, nk, ht0, nh; };
-
-static void g_blocks(std::vector<GRec>& out, int layer, int kt_n, int ht_n,
-                     int bk, int bh) {
-  for (int kt = 0; kt < kt_n; kt += bk)
-    for (int ht = 0; ht < ht_n; ht += bh)
-      out.push_back({layer, kt, kt + bk <= kt_n ? bk : kt_n - kt, ht,
-                     ht + bh <= ht_n ? bh : 1});
-}
-
-// the early jobs (the 38 tiles of the layers 2-4): 19 of two tiles, or fewer
-// with 3 x 1 jobs among them -- level 1: layer 3 as (3, 3, 2) tiles instead of
-// four pairs; levels 2, 3: the columns of one / both output-tile pairs of
-// layer 2 as (3, 2, 2) along k instead of seven 1 x 2 jobs per pair
-static std::vector<GRec> g_early(int level) {
-  std::vector<GRec> out;
-  if (level >= 1) {                              // layer 3 (4 x 2 tiles)
-    out.push_back({2, 0, 3, 0, 1});
-    out.push_back({2, 0, 3, 1, 1});
-    out.push_back({2, 3, 1, 0, 2});
-  } else {
-    g_blocks(out, 2, NB_HT2, NB_HT3, 2, 1);
-  }
-  for (int ht = 0; ht < NB_HT2; ht += 2) {       // layer 2 (7 x 4 tiles)
-    if (level >= 2 + ht / 2) {
-      for (int h = ht; h < ht + 2; ++h) {
-        out.push_back({1, 0, 3, h, 1});
-        out.push_back({1, 3, 2, h, 1});
-        out.push_back({1, 5, 2, h, 1});
-      }
-    } else {
-      for (int kt = 0; kt < NB_HT1; ++kt) out.push_back({1, kt, 1, ht, 2});
-    }
-  }
-  out.push_back({3, 0, 2, 0, 1});                // layer 4 (2 x 1 tiles)
-  return out;
-}
-
-struct GPlan {
-  std::vector<GRec> early, late;
-  std::vector<int> early_slot, late_slot;
-  double span = 1e30;
-};
-
-// the dearest late job to the workgroup that is free first, and so on
-static double g_pair(const std::vector<GRec>& late,
-                     const std::vector<std::pair<double, int>>& free_at,
-                     std::vector<int>& slot_of, int& critical) {
-  std::vector<int> idx(late.size());
-  for (size_t i = 0; i < idx.size(); ++i) idx[i] = (int)i;
-  std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) {
-    return g_cost(late[x].nk, late[x].nh) > g_cost(late[y].nk, late[y].nh);
-  });
-  slot_of.assign(late.size(), -1);
-  double span = 0.0;
-  critical = -1;
-  for (size_t r = 0; r < idx.size(); ++r) {
-    const int j = idx[r];
-    const double end = free_at[r].first + g_cost(late[j].nk, late[j].nh);
-    slot_of[j] = free_at[r].second;
-    if (end > span) { span = end; critical = j; }
-  }
-  return span;
-}
-
-// jobs: records of G_JOB_INTS ints; sched: (early, late) job index per
-// workgroup, -1 = none
-void g_plan(int kt1, std::vector<int>& jobs, std::vector<int>& sched) {
-  const int n_free = XCD_SLOTS - G_ROWT;
-  GPlan best;
-  const int shapes[5][2] = {{2, 1}, {1, 2}, {3, 1}, {2, 2}, {1, 1}};
-  // (experiment switches: force the number of late-only workgroups / the
-  // block shape of the late jobs instead of taking the cost model's choice)
-  const char* e_lo = getenv("NB_TRAIN_LATE_ONLY");
-  const char* e_sh = getenv("NB_TRAIN_LATE_SHAPE");
-  const int f_lo = e_lo != nullptr ? atoi(e_lo) : -1;
-  const int f_sh = e_sh != nullptr ? atoi(e_sh) : -1;
-  for (int late_only = 0; late_only <= 3; ++late_only) {
-    if (f_lo >= 0 && late_only != f_lo) continue;
-    const std::vector<GRec> early = g_early(late_only);
-    if ((int)early.size() + late_only != n_free) continue;
-    // when the workgroups are free for a late job
-    std::vector<std::pair<double, int>> free_at;
-    std::vector<int> early_slot(early.size());
-    double early_end = 0.0;
-    for (int w = 0; w < G_ROWT + late_only; ++w) free_at.push_back({0.0, w});
-    for (size_t i = 0; i < early.size(); ++i) {
-      const int w = G_ROWT + late_only + (int)i;
-      double c = g_cost(early[i].nk, early[i].nh) - G_HEAD;
-      if (c < 0.0) c = 0.0;
-      if (c > early_end) early_end = c;
-      free_at.push_back({c, w});
-      early_slot[i] = w;
-    }
-    std::stable_sort(free_at.begin(), free_at.end(),
-                     [](const std::pair<double, int>& x,
-                        const std::pair<double, int>& y) {
-                       return x.first < y.first;
-                     });
-    for (int si = 0; si < 5; ++si) {
-      if (f_sh >= 0 && si != f_sh) continue;
-      const int* sh = shapes[si];
-      std::vector<GRec> late;
-      g_blocks(late, 0, kt1, NB_HT1, sh[0], sh[1]);
-      while ((int)late.size() <= XCD_SLOTS) {
-        std::vector<int> slot_of;
-        int crit;
-        double span = g_pair(late, free_at, slot_of, crit);
-        if (early_end > span) span = early_end;
-        if (span < best.span - 1e-9) {
-          best.span = span; best.early = early; best.late = late;
-          best.early_slot = early_slot; best.late_slot = slot_of;
-        }
-        GRec& c = late[crit];
-        if (c.nk * c.nh == 1) break;
-        GRec half = c;
-        if (c.nk == 3) { c.nk = 2; half.nk = 1; half.kt0 += 2; }
-        else if (c.nk == 2) { c.nk = 1; half.nk = 1; half.kt0 += 1; }
-        else { c.nh = 1; half.nh = 1; half.ht0 += 1; }
-        late.push_back(half);
-      }
-    }
-  }
-  jobs.clear();
-  sched.clear();
-  if (best.late.empty()) return;   // (the kernel then runs g_jobs_rounds)
-  sched.assign(2 * XCD_SLOTS, -1);
-  for (size_t i = 0; i < best.early.size(); ++i) {
-    const GRec& r = best.early[i];
-    const int rec[G_JOB_INTS] = {r.layer, r.kt0, r.nk, r.ht0, r.nh};
-    sched[2 * best.early_slot[i]] = (int)jobs.size() / G_JOB_INTS;
-    jobs.insert(jobs.end(), rec, rec + G_JOB_INTS);
-  }
-  for (size_t j = 0; j < best.late.size(); ++j) {
-    const GRec& r = best.late[j];
-    const int rec[G_JOB_INTS] = {r.layer, r.kt0, r.nk, r.ht0, r.nh};
-    sched[2 * best.late_slot[j] + 1] = (int)jobs.size() / G_JOB_INTS;
-    jobs.insert(jobs.end(), rec, rec + G_JOB_INTS);
-  }
-}
-
-// transposed copy: tiles [ht][kt], element (hh, kk)
-void put_wt(double* tiles, int kt_n, int k, int h, double v) {
-  tiles[((size_t)(h >> 4) * kt_n + (k >> 4)) * NB_TILE +
-        tile_index(h & 15, k & 15)] = v;
-}
+// the device code's offsets of the transposed tiles are pack_network's
+static_assert(net_layer(1, 1, 1).wt_off == WT2 &&
+              net_layer(2, 1, 1).wt_off == WT3 &&
+              net_layer(3, 1, 1).wt_off == WT4 &&
+              net_layer(4, 1, 1).wt_off == WT_DOUBLES, "transposed tiles");
 
 }  // namespace
+
+// ---- host side -------------------------------------------------------------
+// The environment switches of the trainer, read at every
+// nb_trainer_create_fleet (the tests change them between two trainers of one
+// process).  Only the first is for production, the others serve tests,
+// experiments and debugging; [...]: who uses the switch.
+struct TrainSwitches {
+  // NB_TRAIN_TWO_LAUNCH: two launches per step instead of the resident
+  // kernel, e.g. for several processes on one GPU; emulator.py reads it as
+  // well [INTEGRATION.md, the resident kernel's error message, bench.py,
+  // tests/test_emulator_hparams_gpu.py, tests/sharded_worker.py]
+  bool two_launch;
+  // NB_TRAIN_NO_RESIDENT: the same on the library's side only -- how a
+  // machine without the resident kernel looks to the caller
+  // [tests/test_hip_parity.py, test_emulator_batch_gpu.py, _hparams_gpu.py]
+  bool no_resident;
+  // NB_TRAIN_NO_SCHEDULE: resident kernel with all G jobs behind the barrier,
+  // in rounds [INTEGRATION.md, profiles/r04/second_session/train_slots_*.txt]
+  bool no_schedule;
+  // NB_TRAIN_SYNC_SHIFT=k: the trainer's counters 16 KB + k KB into the block
+  // instead of at its start [profiles/tools/train_sync_shift.py]
+  bool sync_shift;
+  long sync_shift_kb;
+  // NB_TRAIN_BLOCK_SHIFT=k: the block starts k KB into its allocation
+  // [profiles/tools/train_block_shift.py, train_sync_shift.py]
+  bool block_shift;
+  long block_shift_kb;
+  // NB_TRAIN_LATE_ONLY=n, NB_TRAIN_LATE_SHAPE=s: g_plan's forced values, -1 =
+  // the cost model's choice [profiles/tools/train_plan_sweep.py]
+  int late_only, late_shape;
+  // NB_TRAIN_DEBUG: the schedule and the form taken, on stderr
+  // [tests/test_emulator_hparams_gpu.py]
+  bool debug;
+  // NB_TRAIN_DEBUG_BLOCK: the address of the block [profiles/tools/
+  // train_block_shift.py].  sync_arena reads it on its own, once per process
+  // (the timings of the arena's places), as it does NB_TRAIN_SYNC_PLACE=p:
+  // place p for the barrier records of every XCD [INTEGRATION.md]
+  bool debug_block;
+};
+static TrainSwitches train_switches() {
+  auto num = [](const char* name, long unset) {
+    return getenv(name) != nullptr ? atol(getenv(name)) : unset;
+  };
+  TrainSwitches sw;
+  sw.two_launch = getenv("NB_TRAIN_TWO_LAUNCH") != nullptr;
+  sw.no_resident = getenv("NB_TRAIN_NO_RESIDENT") != nullptr;
+  sw.no_schedule = getenv("NB_TRAIN_NO_SCHEDULE") != nullptr;
+  sw.sync_shift = getenv("NB_TRAIN_SYNC_SHIFT") != nullptr;
+  sw.sync_shift_kb = num("NB_TRAIN_SYNC_SHIFT", 0);
+  sw.block_shift = getenv("NB_TRAIN_BLOCK_SHIFT") != nullptr;
+  sw.block_shift_kb = num("NB_TRAIN_BLOCK_SHIFT", 0);
+  sw.late_only = (int)num("NB_TRAIN_LATE_ONLY", -1);
+  sw.late_shape = (int)num("NB_TRAIN_LATE_SHAPE", -1);
+  sw.debug = getenv("NB_TRAIN_DEBUG") != nullptr;
+  sw.debug_block = getenv("NB_TRAIN_DEBUG_BLOCK") != nullptr;
+  return sw;
+}
 
 // One-time check of the placement the resident kernel relies on: workgroups
 // i, i + 8, i + 16, ... of a 1-D grid run on the same XCD.
@@ -2050,22 +1911,19 @@ static bool sync_arena() {
 
 struct nb_trainer {
   int n_dim = 0, E = 0, kt1 = 0, dt = 0;
-  long long n = 0;
   long long n_w = 0;
-  const double* X = nullptr;       // network 0's set (all networks', if shared)
-  const double* y = nullptr;
   // per network: training set and rows (a fleet: the networks of several
   // ensembles, each with the set of its ensemble)
   std::vector<const double*> Xs, ys;
   std::vector<long long> ns;
-  bool shared_set = true;
+  bool shared_set = true;          // all networks have network 0's set
   std::vector<NetState> nets_host;
   NetState* nets_dev = nullptr;
   double* pool = nullptr;          // one allocation for all per-net buffers
   int max_iter = 10000, n_iter_no_change = 10, batch = 200;
   double tol = 0.0, lr = 1e-2, b1 = 0.9, b2 = 0.999, eps = 1e-8;
   long long t_adam = 0;
-  char* block = nullptr;           // the one device allocation (see create)
+  char* block = nullptr;           // the one device allocation (alloc_block)
   char* block_alloc = nullptr;
   int* sync_dev = nullptr;         // per network: counter, error, xcc mask
   int* jobs_dev = nullptr;         // job list of the G phase
@@ -2092,14 +1950,224 @@ struct nb_trainer {
   long long n_tickets = 0;
 };
 
-extern "C" {
+// ---- nb_trainer_create_fleet, step by step ---------------------------------
+static int check_shape(int n_dim, int n_networks, const int64_t* n_rows_of) {
+  if (n_dim < 1 || n_dim > 16 * NB_MAX_DT || n_networks < 1) {
+    nb_set_error("bad trainer shape (n_dim=%d, n_networks=%d)", n_dim,
+                 n_networks);
+    return NB_ERR_ARG;
+  }
+  for (int i = 0; i < n_networks; ++i)
+    if (n_rows_of[i] < 1) {
+      nb_set_error("bad trainer shape (network %d has %lld rows)", i,
+                   (long long)n_rows_of[i]);
+      return NB_ERR_ARG;
+    }
+  return NB_OK;
+}
 
-int nb_trainer_create_fleet(int32_t n_dim, int32_t n_networks,
-                            const int64_t* n_rows_of,
-                            const double* const* x_dev_of,
-                            const double* const* y_dev_of,
-                            const double* const* coefs,
-                            const double* const* icpts, nb_trainer** out);
+// the job lists of the G phase: of the forms without a schedule, and of the
+// resident kernel's schedule with the schedule itself (empty: there is none)
+struct TrainPlan {
+  std::vector<int> jobs, sched_jobs, sched;
+};
+static void print_plan(const TrainPlan& p) {
+  for (size_t w = 0; 2 * w + 1 < p.sched.size(); ++w)
+    for (int r = 0; r < 2; ++r) {
+      const int j = p.sched[2 * w + r];
+      if (j >= 0)
+        fprintf(stderr, "[trainer] workgroup %2d %s job: layer %d, k-tiles "
+                "%d+%d, h-tiles %d+%d\n", (int)w, r == 0 ? "early" : "late ",
+                p.sched_jobs[5 * j] + 1, p.sched_jobs[5 * j + 1],
+                p.sched_jobs[5 * j + 2], p.sched_jobs[5 * j + 3],
+                p.sched_jobs[5 * j + 4]);
+    }
+}
+
+// ONE allocation for everything the kernels touch -- [barrier counters, 12
+// KB][network records, 1 KB][job lists, 1 + 2 KB][weights, moments, stash, loss
+// curve and scalars of every network] -- so that the small arrays lie the
+// same way relative to each other and to the pool in every process (as
+// separate allocations they landed wherever the allocator had a slot, and
+// the step time followed).
+constexpr size_t OFF_NETS = 12288, OFF_JOBS = 13312, OFF_SCHED = 14336,
+                 OFF_SYNC2 = 16384, OFF_POOL = 32768;
+static_assert(SYNC_INTS * sizeof(int) <= OFF_NETS &&
+              MAX_RESIDENT * sizeof(NetState) <= OFF_JOBS - OFF_NETS,
+              "trainer block layout");
+// a network's part of the pool, in doubles: W, M, V, WT, then these
+struct PoolLayout { long long stash, curve, per_net; };
+static PoolLayout pool_layout(const nb_trainer* t) {
+  const long long stash =
+      (long long)MAXB * (16 * t->kt1 + 2 * (LD1 + LD2 + LD3) + LD4);
+  const long long curve = (t->max_iter + 1) & ~1LL;   // 16-byte alignment
+  // (a multiple of 4 KB: no line of one network's record next to another's)
+  return {stash, curve,
+          (3 * t->n_w + WT_DOUBLES + stash + curve + 32 + 511) / 512 * 512};
+}
+
+// allocates the block, points the trainer into it and uploads the job lists
+static int alloc_block(nb_trainer* t, const TrainSwitches& sw,
+                       const TrainPlan& plan) {
+  const bool use_sched = !plan.sched.empty() && !sw.no_schedule;
+  // [sched (2 per workgroup)][its job records]
+  std::vector<int> sched = plan.sched;
+  sched.insert(sched.end(), plan.sched_jobs.begin(), plan.sched_jobs.end());
+  // (with the NB_TRAIN_SYNC_SHIFT experiment the counters sit at OFF_SYNC2,
+  // inside the schedule's slot: the schedule then has to end in front of them)
+  const size_t sched_end = sw.sync_shift ? OFF_SYNC2 : OFF_POOL;
+  if (plan.jobs.size() * sizeof(int) > OFF_SCHED - OFF_JOBS ||
+      sched.size() * sizeof(int) > sched_end - OFF_SCHED) {
+    nb_set_error("trainer: job lists exceed their slots");
+    return NB_ERR_ARG;
+  }
+  // (whole 2 MB fragments: the mapping of a block that ends inside one was
+  // seen to cost up to a microsecond per step)
+  const size_t bytes =
+      (OFF_POOL + (size_t)t->per_net * t->E * sizeof(double) +
+       (2u << 20) - 1) / (2u << 20) * (2u << 20);
+  const size_t shift = sw.block_shift ? (size_t)sw.block_shift_kb * 1024 : 0;
+  const size_t slack = sw.block_shift ? (2u << 20) : 0;
+  hipError_t e = hipMalloc((void**)&t->block_alloc, bytes + slack);
+  if (e == hipSuccess) e = hipMemset(t->block_alloc, 0, bytes + slack);
+  if (e == hipSuccess) {
+    t->block = t->block_alloc + shift;
+    if (sw.debug_block)
+      fprintf(stderr, "[trainer] block at %p\n", (void*)t->block);
+    t->sync_dev = (int*)t->block;
+    if (sw.sync_shift)
+      t->sync_dev = (int*)(t->block + OFF_SYNC2 +
+                           (size_t)sw.sync_shift_kb * 1024);
+    t->nets_dev = (NetState*)(t->block + OFF_NETS);
+    t->jobs_dev = (int*)(t->block + OFF_JOBS);
+    t->pool = (double*)(t->block + OFF_POOL);
+    e = hipMemcpy(t->jobs_dev, plan.jobs.data(),
+                  plan.jobs.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess && use_sched) {
+      t->sched_dev = (int*)(t->block + OFF_SCHED);
+      e = hipMemcpy(t->sched_dev, sched.data(), sched.size() * sizeof(int),
+                    hipMemcpyHostToDevice);
+    }
+  }
+  if (e != hipSuccess) {
+    nb_set_error("trainer allocation failed: %s", hipGetErrorString(e));
+    return NB_ERR_HIP;
+  }
+  return NB_OK;
+}
+
+// A resident network takes one workgroup slot on every CU of an XCD (of two
+// per CU).  Every trainer owns its XCDs exclusively -- two resident kernels
+// that each hold a part of an XCD could wait for each other -- and puts
+// one network on each while they last, two beyond that (16 networks on the
+// 8 XCDs); a trainer that finds too few free XCDs trains with two launches
+// per step instead.
+static void assign_xcds(nb_trainer* t, const TrainSwitches& sw) {
+  const int n_networks = t->E;
+  t->two_launch = n_networks > MAX_RESIDENT || sw.two_launch ||
+                  sw.no_resident || !xcd_pinning_available();
+  t->xcd_map.n_nets = n_networks;
+  for (int x = 0; x < XCD_COUNT; ++x)
+    t->xcd_map.net[x][0] = t->xcd_map.net[x][1] = -1;
+  if (t->two_launch) return;
+  int n_free = 0;
+  for (int x = 0; x < XCD_COUNT; ++x)
+    if (!(g_xcd_in_use & (1u << x))) ++n_free;
+  if (n_networks > 2 * n_free) {
+    t->two_launch = true;
+    return;
+  }
+  // as many XCDs as there are networks (up to the free ones), the
+  // networks dealt out round-robin
+  const int n_use = n_networks < n_free ? n_networks : n_free;
+  int xs_used[XCD_COUNT], k = 0;
+  for (int x = 0; x < XCD_COUNT && k < n_use; ++x)
+    if (!(g_xcd_in_use & (1u << x))) xs_used[k++] = x;
+  for (int i = 0; i < n_networks; ++i)
+    t->xcd_map.net[xs_used[i % n_use]][i / n_use] = i;
+  for (int j = 0; j < n_use; ++j) t->xcd_owned |= 1u << xs_used[j];
+  g_xcd_in_use |= t->xcd_owned;
+}
+
+// the records of the networks, and their weights in tiles (nb_train_plan.h)
+static int upload_networks(nb_trainer* t, const PoolLayout& lay,
+                           const double* const* coefs,
+                           const double* const* icpts) {
+  hipError_t e = hipSuccess;
+  std::vector<double> w, wt;
+  for (int i = 0; i < t->E; ++i) {
+    NetState s;
+    double* base = t->pool + (size_t)i * lay.per_net;
+    s.W = (nb_gd*)base; s.M = s.W + t->n_w; s.V = s.M + t->n_w;
+    s.WT = s.V + t->n_w;
+    s.stash = s.WT + WT_DOUBLES;
+    t->pool_stash.push_back(s.stash);
+    s.loss_curve = s.stash + lay.stash;
+    s.scal = s.loss_curve + lay.curve;
+    t->nets_host.push_back(s);
+    pack_network(t->n_dim, t->kt1, coefs + 4 * i, icpts + 4 * i, w, wt);
+    e = hipMemcpy((void*)s.W, w.data(), w.size() * sizeof(double),
+                  hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+      e = hipMemcpy((void*)s.WT, wt.data(), wt.size() * sizeof(double),
+                    hipMemcpyHostToDevice);
+    const double scal0[8] = {0.0, INFINITY, 0.0, 0.0, 0.0, 0.0, 0, 0};
+    if (e == hipSuccess)
+      e = hipMemcpy((void*)s.scal, scal0, sizeof scal0, hipMemcpyHostToDevice);
+    if (e != hipSuccess) break;
+  }
+  if (e == hipSuccess)
+    e = hipMemcpy(t->nets_dev, t->nets_host.data(),
+                  t->E * sizeof(NetState), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    nb_set_error("trainer upload failed: %s", hipGetErrorString(e));
+    return NB_ERR_HIP;
+  }
+  return NB_OK;
+}
+
+// The status of a chunk of epochs.  sync: the trainer's sync array behind the
+// chunk, with the error word of every network's barriers (resident form;
+// null otherwise); scal: the 8 scalars of every network.  status: n_iter,
+// negative where the network has stopped.
+static int chunk_status(const nb_trainer* t, const int* sync,
+                        const double* scal, int32_t* status_host) {
+  for (int i = 0; sync != nullptr && i < t->E; ++i)
+    if (sync[SYNC_WORDS * i + 1] != 0) {
+      nb_set_error("resident training kernel failed for network %d (%s); "
+                   "set NB_TRAIN_TWO_LAUNCH=1 to train with two launches "
+                   "per step", i,
+                   sync[SYNC_WORDS * i + 1] == 2
+                       ? "its workgroups do not share an XCD"
+                       : "barrier timeout");
+      return NB_ERR_HIP;
+    }
+  for (int i = 0; i < t->E; ++i) {
+    const int n_iter = (int)scal[8 * i + 3];
+    status_host[i] = (scal[8 * i + 4] != 0.0) ? -n_iter : n_iter;
+  }
+  return NB_OK;
+}
+
+// launches KERNEL<kt1, large> (kt1 1-9); false: there is none for this kt1
+#define NB_LAUNCH_CASE(KERNEL, KT1_, ...)                                  \
+  case KT1_:                                                               \
+    if (large_) hipLaunchKernelGGL((KERNEL<KT1_, true>), __VA_ARGS__);     \
+    else hipLaunchKernelGGL((KERNEL<KT1_, false>), __VA_ARGS__);           \
+    return true;
+#define NB_LAUNCH_KT1_LARGE(KERNEL, kt1, large, ...)                       \
+  [&, large_ = (large)]() {                                                \
+    switch (kt1) {                                                         \
+      NB_LAUNCH_CASE(KERNEL, 1, __VA_ARGS__) NB_LAUNCH_CASE(KERNEL, 2, __VA_ARGS__) \
+      NB_LAUNCH_CASE(KERNEL, 3, __VA_ARGS__) NB_LAUNCH_CASE(KERNEL, 4, __VA_ARGS__) \
+      NB_LAUNCH_CASE(KERNEL, 5, __VA_ARGS__) NB_LAUNCH_CASE(KERNEL, 6, __VA_ARGS__) \
+      NB_LAUNCH_CASE(KERNEL, 7, __VA_ARGS__) NB_LAUNCH_CASE(KERNEL, 8, __VA_ARGS__) \
+      NB_LAUNCH_CASE(KERNEL, 9, __VA_ARGS__)                               \
+    }                                                                      \
+    return false;                                                          \
+  }()
+
+extern "C" {
 
 int nb_trainer_create(int32_t n_dim, int32_t n_networks, int64_t n_rows,
                       const double* x_dev, const double* y_dev,
@@ -2122,222 +2190,47 @@ int nb_trainer_create_fleet(int32_t n_dim, int32_t n_networks,
                             const double* const* y_dev_of,
                             const double* const* coefs,
                             const double* const* icpts, nb_trainer** out) {
-  if (n_dim < 1 || n_dim > 16 * NB_MAX_DT || n_networks < 1) {
-    nb_set_error("bad trainer shape (n_dim=%d, n_networks=%d)", n_dim,
-                 n_networks);
-    return NB_ERR_ARG;
-  }
-  for (int i = 0; i < n_networks; ++i)
-    if (n_rows_of[i] < 1) {
-      nb_set_error("bad trainer shape (network %d has %lld rows)", i,
-                   (long long)n_rows_of[i]);
-      return NB_ERR_ARG;
-    }
-  const int64_t n_rows = n_rows_of[0];
-  const double* x_dev = x_dev_of[0];
-  const double* y_dev = y_dev_of[0];
+  int rc = check_shape(n_dim, n_networks, n_rows_of);
+  if (rc != NB_OK) return rc;
+  const TrainSwitches sw = train_switches();
   nb_trainer* t = new nb_trainer();
-  t->n_dim = n_dim; t->E = n_networks; t->n = n_rows;
+  t->n_dim = n_dim; t->E = n_networks;
   t->dt = (n_dim + 15) / 16;
   t->kt1 = (n_dim + 1 + 15) / 16;
-  t->X = x_dev; t->y = y_dev;
   for (int i = 0; i < n_networks; ++i) {
     t->Xs.push_back(x_dev_of[i]); t->ys.push_back(y_dev_of[i]);
     t->ns.push_back(n_rows_of[i]);
-    if (x_dev_of[i] != x_dev || y_dev_of[i] != y_dev || n_rows_of[i] != n_rows)
+    if (x_dev_of[i] != x_dev_of[0] || y_dev_of[i] != y_dev_of[0] ||
+        n_rows_of[i] != n_rows_of[0])
       t->shared_set = false;
   }
   t->n_w = (long long)nb_net_tiles(t->kt1) * NB_TILE;
-  const long long stash = (long long)MAXB * (16 * t->kt1 + 2 * (LD1 + LD2 + LD3) + LD4);
-  const long long curve = (t->max_iter + 1) & ~1LL;   // 16-byte alignment
-  // (a multiple of 4 KB: no line of one network's record next to another's)
-  const long long per_net =
-      (3 * t->n_w + WT_DOUBLES + stash + curve + 32 + 511) / 512 * 512;
-  t->per_net = per_net;
-  // ONE allocation for everything the kernels touch -- [barrier counters, 12
-  // KB][network records, 1 KB][job lists, 1 + 2 KB][weights, moments, stash, loss
-  // curve and scalars of every network] -- so that the small arrays lie the
-  // same way relative to each other and to the pool in every process (as
-  // separate allocations they landed wherever the allocator had a slot, and
-  // the step time followed).
-  const std::vector<int> jobs = g_jobs_rounds(t->kt1);
-  t->n_jobs = (int)jobs.size() / G_JOB_INTS;
-  // (NB_TRAIN_NO_SCHEDULE: all jobs behind the barrier, for comparison)
-  std::vector<int> sjobs, sched;
-  g_plan(t->kt1, sjobs, sched);
-  const bool use_sched =
-      !sched.empty() && getenv("NB_TRAIN_NO_SCHEDULE") == nullptr;
-  // [sched (2 per workgroup)][its job records]
-  sched.insert(sched.end(), sjobs.begin(), sjobs.end());
-  constexpr size_t OFF_NETS = 12288, OFF_JOBS = 13312, OFF_SCHED = 14336,
-                   OFF_SYNC2 = 16384, OFF_POOL = 32768;
-  static_assert(SYNC_INTS * sizeof(int) <= OFF_NETS &&
-                MAX_RESIDENT * sizeof(NetState) <= OFF_JOBS - OFF_NETS,
-                "trainer block layout");
-  // (with the NB_TRAIN_SYNC_SHIFT experiment the counters sit at OFF_SYNC2,
-  // inside the schedule's slot: the schedule then has to end in front of them)
-  const size_t sched_end =
-      getenv("NB_TRAIN_SYNC_SHIFT") != nullptr ? OFF_SYNC2 : OFF_POOL;
-  if (jobs.size() * sizeof(int) > OFF_SCHED - OFF_JOBS ||
-      sched.size() * sizeof(int) > sched_end - OFF_SCHED) {
-    nb_set_error("trainer: job lists exceed their slots");
-    delete t;
-    return NB_ERR_ARG;
-  }
-  // (whole 2 MB fragments: the mapping of a block that ends inside one was
-  // seen to cost up to a microsecond per step)
-  const size_t bytes =
-      (OFF_POOL + (size_t)per_net * n_networks * sizeof(double) +
-       (2u << 20) - 1) / (2u << 20) * (2u << 20);
-  // (NB_TRAIN_BLOCK_SHIFT: experiment -- the block starts that many KB into
-  // its allocation)
-  const size_t shift = getenv("NB_TRAIN_BLOCK_SHIFT")
-      ? (size_t)atol(getenv("NB_TRAIN_BLOCK_SHIFT")) * 1024 : 0;
-  const size_t slack = getenv("NB_TRAIN_BLOCK_SHIFT") ? (2u << 20) : 0;
-  hipError_t e = hipMalloc((void**)&t->block_alloc, bytes + slack);
-  if (e == hipSuccess) e = hipMemset(t->block_alloc, 0, bytes + slack);
-  if (e == hipSuccess) {
-    t->block = t->block_alloc + shift;
-    if (getenv("NB_TRAIN_DEBUG_BLOCK") != nullptr)
-      fprintf(stderr, "[trainer] block at %p\n", (void*)t->block);
-    // (NB_TRAIN_SYNC_SHIFT: experiment -- the counters 16 KB + that many KB
-    // into the block instead of at its start)
-    t->sync_dev = (int*)t->block;
-    if (getenv("NB_TRAIN_SYNC_SHIFT"))
-      t->sync_dev = (int*)(t->block + OFF_SYNC2 +
-                           (size_t)atol(getenv("NB_TRAIN_SYNC_SHIFT")) * 1024);
-    t->nets_dev = (NetState*)(t->block + OFF_NETS);
-    t->jobs_dev = (int*)(t->block + OFF_JOBS);
-    t->pool = (double*)(t->block + OFF_POOL);
-    e = hipMemcpy(t->jobs_dev, jobs.data(), jobs.size() * sizeof(int),
-                  hipMemcpyHostToDevice);
-    if (e == hipSuccess && use_sched) {
-      t->sched_dev = (int*)(t->block + OFF_SCHED);
-      e = hipMemcpy(t->sched_dev, sched.data(), sched.size() * sizeof(int),
-                    hipMemcpyHostToDevice);
+  const PoolLayout lay = pool_layout(t);
+  t->per_net = lay.per_net;
+  TrainPlan plan;
+  plan.jobs = g_jobs_rounds(t->kt1);
+  g_plan(t->kt1, sw.late_only, sw.late_shape, plan.sched_jobs, plan.sched);
+  t->n_jobs = (int)plan.jobs.size() / G_JOB_INTS;
+  rc = alloc_block(t, sw, plan);
+  if (rc == NB_OK) {
+    assign_xcds(t, sw);
+    if (t->two_launch && !t->shared_set) {
+      nb_set_error("a trainer whose networks have different training sets "
+                   "needs the resident kernel (at most %d networks, free XCDs, "
+                   "NB_TRAIN_TWO_LAUNCH unset)", MAX_RESIDENT);
+      rc = NB_ERR_UNSUPPORTED;
     }
   }
-  // (NB_TRAIN_NO_RESIDENT: the library-side switch only, for the test of the
-  // host's fallback when the resident kernel is not to be had)
-  t->two_launch = n_networks > MAX_RESIDENT ||
-                  getenv("NB_TRAIN_TWO_LAUNCH") != nullptr ||
-                  getenv("NB_TRAIN_NO_RESIDENT") != nullptr ||
-                  !xcd_pinning_available();
-  // A resident network takes one workgroup slot on every CU of an XCD (of two
-  // per CU).  Every trainer owns its XCDs exclusively -- two resident kernels
-  // that each hold a part of an XCD could wait for each other -- and puts
-  // one network on each while they last, two beyond that (16 networks on the
-  // 8 XCDs); a trainer that finds too few free XCDs trains with two launches
-  // per step instead.
-  t->xcd_map.n_nets = n_networks;
-  for (int x = 0; x < XCD_COUNT; ++x)
-    t->xcd_map.net[x][0] = t->xcd_map.net[x][1] = -1;
-  if (!t->two_launch) {
-    int n_free = 0;
-    for (int x = 0; x < XCD_COUNT; ++x)
-      if (!(g_xcd_in_use & (1u << x))) ++n_free;
-    if (n_networks > 2 * n_free) {
-      t->two_launch = true;
-    } else {
-      // as many XCDs as there are networks (up to the free ones), the
-      // networks dealt out round-robin
-      const int n_use = n_networks < n_free ? n_networks : n_free;
-      int xs_used[XCD_COUNT], k = 0;
-      for (int x = 0; x < XCD_COUNT && k < n_use; ++x)
-        if (!(g_xcd_in_use & (1u << x))) xs_used[k++] = x;
-      for (int i = 0; i < n_networks; ++i)
-        t->xcd_map.net[xs_used[i % n_use]][i / n_use] = i;
-      for (int j = 0; j < n_use; ++j) t->xcd_owned |= 1u << xs_used[j];
-      g_xcd_in_use |= t->xcd_owned;
-    }
-  }
-  if (t->two_launch && !t->shared_set) {
-    nb_set_error("a trainer whose networks have different training sets "
-                 "needs the resident kernel (at most %d networks, free XCDs, "
-                 "NB_TRAIN_TWO_LAUNCH unset)", MAX_RESIDENT);
-    nb_trainer_destroy(t);
-    return NB_ERR_UNSUPPORTED;
-  }
-  if (getenv("NB_TRAIN_DEBUG") != nullptr) {
-    std::vector<int> sjobs, sched;
-    g_plan(t->kt1, sjobs, sched);
-    for (size_t w = 0; 2 * w + 1 < sched.size(); ++w)
-      for (int r = 0; r < 2; ++r) {
-        const int j = sched[2 * w + r];
-        if (j >= 0)
-          fprintf(stderr, "[trainer] workgroup %2d %s job: layer %d, k-tiles "
-                  "%d+%d, h-tiles %d+%d\n", (int)w, r == 0 ? "early" : "late ",
-                  sjobs[5 * j] + 1, sjobs[5 * j + 1], sjobs[5 * j + 2],
-                  sjobs[5 * j + 3], sjobs[5 * j + 4]);
-      }
-  }
-  if (getenv("NB_TRAIN_DEBUG") != nullptr)
+  if (rc == NB_OK && sw.debug) {
+    print_plan(plan);
     fprintf(stderr, "[trainer] nets=%d n=%lld two_launch=%d owned=%02x in_use=%02x\n",
-            n_networks, (long long)n_rows, (int)t->two_launch, t->xcd_owned,
-            g_xcd_in_use);
-  if (e != hipSuccess) {
-    nb_set_error("trainer allocation failed: %s", hipGetErrorString(e));
-    nb_trainer_destroy(t);
-    return NB_ERR_HIP;
+            n_networks, (long long)n_rows_of[0], (int)t->two_launch,
+            t->xcd_owned, g_xcd_in_use);
   }
-  std::vector<double> w((size_t)t->n_w);
-  for (int i = 0; i < n_networks; ++i) {
-    NetState s;
-    double* base = t->pool + (size_t)i * per_net;
-    s.W = (nb_gd*)base; s.M = s.W + t->n_w; s.V = s.M + t->n_w;
-    s.WT = s.V + t->n_w;
-    s.stash = s.WT + WT_DOUBLES;
-    t->pool_stash.push_back(s.stash);
-    s.loss_curve = s.stash + stash;
-    s.scal = s.loss_curve + curve;
-    t->nets_host.push_back(s);
-    std::fill(w.begin(), w.end(), 0.0);
-    double* w1 = w.data();
-    double* w2 = w1 + (size_t)t->kt1 * NB_HT1 * NB_TILE;
-    double* w3 = w2 + (size_t)NB_HT1 * NB_HT2 * NB_TILE;
-    double* w4 = w3 + (size_t)NB_HT2 * NB_HT3 * NB_TILE;
-    const double* const* c = coefs + 4 * i;
-    const double* const* b = icpts + 4 * i;
-    for (int k = 0; k < n_dim; ++k)
-      for (int h = 0; h < NB_H1; ++h) put_w(w1, NB_HT1, k, h, c[0][(size_t)k * NB_H1 + h]);
-    for (int h = 0; h < NB_H1; ++h) put_w(w1, NB_HT1, n_dim, h, b[0][h]);
-    for (int k = 0; k < NB_H1; ++k)
-      for (int h = 0; h < NB_H2; ++h) put_w(w2, NB_HT2, k, h, c[1][(size_t)k * NB_H2 + h]);
-    for (int h = 0; h < NB_H2; ++h) put_w(w2, NB_HT2, NB_H1, h, b[1][h]);
-    for (int k = 0; k < NB_H2; ++k)
-      for (int h = 0; h < NB_H3; ++h) put_w(w3, NB_HT3, k, h, c[2][(size_t)k * NB_H3 + h]);
-    for (int h = 0; h < NB_H3; ++h) put_w(w3, NB_HT3, NB_H2, h, b[2][h]);
-    for (int k = 0; k < NB_H3; ++k) put_w(w4, 1, k, 0, c[3][k]);
-    put_w(w4, 1, NB_H3, 0, b[3][0]);
-    e = hipMemcpy((void*)s.W, w.data(), (size_t)t->n_w * sizeof(double),
-                  hipMemcpyHostToDevice);
-    {
-      // transposed tiles of layers 2-4 (the backward pass's operands)
-      std::vector<double> wt((size_t)WT_DOUBLES, 0.0);
-      for (int k = 0; k <= NB_H1; ++k)
-        for (int h = 0; h < NB_H2; ++h)
-          put_wt(wt.data() + WT2, NB_HT1, k, h, get_w(w2, NB_HT2, k, h));
-      for (int k = 0; k <= NB_H2; ++k)
-        for (int h = 0; h < NB_H3; ++h)
-          put_wt(wt.data() + WT3, NB_HT2, k, h, get_w(w3, NB_HT3, k, h));
-      for (int k = 0; k <= NB_H3; ++k)
-        put_wt(wt.data() + WT4, NB_HT3, k, 0, get_w(w4, 1, k, 0));
-      if (e == hipSuccess)
-        e = hipMemcpy((void*)s.WT, wt.data(), wt.size() * sizeof(double),
-                      hipMemcpyHostToDevice);
-    }
-    const double scal0[8] = {0.0, INFINITY, 0.0, 0.0, 0.0, 0.0, 0, 0};
-    if (e == hipSuccess)
-      e = hipMemcpy((void*)s.scal, scal0, sizeof scal0, hipMemcpyHostToDevice);
-    if (e != hipSuccess) break;
-  }
-  if (e == hipSuccess)
-    e = hipMemcpy(t->nets_dev, t->nets_host.data(),
-                  n_networks * sizeof(NetState), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    nb_set_error("trainer upload failed: %s", hipGetErrorString(e));
+  if (rc == NB_OK) rc = upload_networks(t, lay, coefs, icpts);
+  if (rc != NB_OK) {
     nb_trainer_destroy(t);
-    return NB_ERR_HIP;
+    return rc;
   }
   *out = t;
   return NB_OK;
@@ -2362,22 +2255,23 @@ int nb_trainer_set_hparams(nb_trainer* t, double lr, double beta1,
   for (long long n : t->ns) eff = std::max(eff, std::min(n, (long long)batch));
   const bool large = eff > SMALL_BATCH;
   const int rowt = large ? (int)((eff + 15) / 16) : G_ROWT;
+  // doubles of one network in a large stash of `rt` row tiles
+  auto per_net = [&](int rt) {
+    return (stash_doubles(16LL * rt, 16 * t->kt1) + rt + 511) / 512 * 512;
+  };
   if (large != t->large || (large && rowt > t->big_rowt)) {
     NB_HIP_CHECK(hipDeviceSynchronize());
     if (large && rowt > t->big_rowt) {
       if (t->big_stash) NB_HIP_CHECK(hipFree(t->big_stash));
       t->big_stash = nullptr;
       t->big_rowt = 0;
-      const long long per = (stash_doubles(16LL * rowt, 16 * t->kt1) + rowt +
-                             511) / 512 * 512;
-      const size_t bytes = (size_t)per * t->E * sizeof(double);
+      const size_t bytes = (size_t)per_net(rowt) * t->E * sizeof(double);
       NB_HIP_CHECK(hipMalloc((void**)&t->big_stash, bytes));
       // (finite contents: G scales the rows past a minibatch by zero)
       NB_HIP_CHECK(hipMemset(t->big_stash, 0, bytes));
       t->big_rowt = rowt;
     }
-    const long long per = (stash_doubles(16LL * t->big_rowt, 16 * t->kt1) +
-                           t->big_rowt + 511) / 512 * 512;
+    const long long per = per_net(t->big_rowt);
     for (int i = 0; i < t->E; ++i)
       t->nets_host[i].stash = large ? (nb_gd*)(t->big_stash + (size_t)i * per)
                                     : t->pool_stash[i];
@@ -2394,9 +2288,6 @@ int nb_trainer_set_hparams(nb_trainer* t, double lr, double beta1,
   return NB_OK;
 }
 
-int nb_trainer_run_fleet(nb_trainer* t, const int32_t* const* perm_dev_of,
-                         int32_t n_epochs, int32_t* status_host, void* stream);
-
 int nb_trainer_run(nb_trainer* t, const int32_t* perm_dev, int32_t n_epochs,
                    int32_t* status_host, void* stream) {
   if (!t->shared_set) {
@@ -2406,7 +2297,7 @@ int nb_trainer_run(nb_trainer* t, const int32_t* perm_dev, int32_t n_epochs,
   }
   std::vector<const int32_t*> perms((size_t)t->E);
   for (int i = 0; i < t->E; ++i)
-    perms[i] = perm_dev + (size_t)i * n_epochs * t->n;
+    perms[i] = perm_dev + (size_t)i * n_epochs * t->ns[0];
   return nb_trainer_run_fleet(t, perms.data(), n_epochs, status_host, stream);
 }
 
@@ -2414,19 +2305,20 @@ int nb_trainer_run_fleet(nb_trainer* t, const int32_t* const* perm_dev_of,
                          int32_t n_epochs, int32_t* status_host,
                          void* stream) {
   hipStream_t s = (hipStream_t)stream;
+  const long long n = t->ns[0];
   TrainArgs a;
-  a.nets = t->nets_dev; a.X = (const nb_gd*)t->X; a.y = (const nb_gd*)t->y;
+  a.nets = t->nets_dev;
+  a.X = (const nb_gd*)t->Xs[0]; a.y = (const nb_gd*)t->ys[0];
   a.perm = (const nb_gi*)perm_dev_of[0];
   a.jobs = (const nb_gi*)t->jobs_dev; a.n_jobs = t->n_jobs;
   // (LARGE: every workgroup has row tiles -- the jobs go behind the barrier)
   a.sched = t->large ? nullptr : (const nb_gi*)t->sched_dev;
   a.rowt = t->rowt;
   a.sched_jobs = a.sched ? a.sched + 2 * XCD_SLOTS : nullptr;
-  a.n = t->n; a.n_dim = t->n_dim; a.kt1 = t->kt1; a.n_epochs = n_epochs;
+  a.n = n; a.n_dim = t->n_dim; a.kt1 = t->kt1; a.n_epochs = n_epochs;
   a.max_iter = t->max_iter; a.n_iter_no_change = t->n_iter_no_change;
-  a.batch = (int)((t->n < t->batch) ? t->n : t->batch);
+  a.batch = (int)((n < t->batch) ? n : t->batch);
   a.tol = t->tol; a.lr = t->lr; a.b1 = t->b1; a.b2 = t->b2; a.eps = t->eps;
-  const long long n = t->n;
   const int steps_per_epoch = (int)((n + a.batch - 1) / a.batch);
   if (!t->two_launch) {
     FleetData fleet;
@@ -2456,20 +2348,10 @@ int nb_trainer_run_fleet(nb_trainer* t, const int32_t* const* perm_dev_of,
     // 32 workgroups per XCD: all of them for its network, or 16 for each of
     // its two
     const dim3 grid(XCD_COUNT * XCD_SLOTS), blk(256);
-    switch (t->kt1) {
-#define NB_CASE(KT1_)                                                      \
-      case KT1_:                                                           \
-        if (t->large)                                                      \
-          hipLaunchKernelGGL((nb_train_xcd_kernel<KT1_, true>), grid, blk, \
-                             0, s, a, fleet, t->xcd_map, tab, t->sync_dev); \
-        else                                                               \
-          hipLaunchKernelGGL((nb_train_xcd_kernel<KT1_, false>), grid, blk,\
-                             0, s, a, fleet, t->xcd_map, tab, t->sync_dev); \
-        break;
-      NB_CASE(1) NB_CASE(2) NB_CASE(3) NB_CASE(4) NB_CASE(5)
-      NB_CASE(6) NB_CASE(7) NB_CASE(8) NB_CASE(9)
-#undef NB_CASE
-      default: nb_set_error("n_dim unsupported"); return NB_ERR_UNSUPPORTED;
+    if (!NB_LAUNCH_KT1_LARGE(nb_train_xcd_kernel, t->kt1, t->large, grid, blk,
+                             0, s, a, fleet, t->xcd_map, tab, t->sync_dev)) {
+      nb_set_error("n_dim unsupported");
+      return NB_ERR_UNSUPPORTED;
     }
     t->t_adam += (long long)n_epochs * steps_per_epoch;
     NB_HIP_CHECK(hipGetLastError());
@@ -2479,7 +2361,7 @@ int nb_trainer_run_fleet(nb_trainer* t, const int32_t* const* perm_dev_of,
   }
   // two launches per step: one training set, contiguous shuffles
   for (int i = 1; i < t->E; ++i)
-    if (perm_dev_of[i] != perm_dev_of[0] + (size_t)i * n_epochs * t->n) {
+    if (perm_dev_of[i] != perm_dev_of[0] + (size_t)i * n_epochs * n) {
       nb_set_error("two-launch training needs the shuffles of all networks "
                    "in one (E, n_epochs, n) array");
       return NB_ERR_ARG;
@@ -2493,20 +2375,10 @@ int nb_trainer_run_fleet(nb_trainer* t, const int32_t* const* perm_dev_of,
       const dim3 gfb(t->large ? (nb + 15) / 16 : G_ROWT, t->E),
           gg(t->n_jobs, t->E), blk(256);
       t->t_adam += 1;
-      switch (t->kt1) {
-#define NB_CASE(KT1_)                                                      \
-        case KT1_:                                                         \
-          if (t->large)                                                    \
-            hipLaunchKernelGGL((nb_train_fb_kernel<KT1_, true>), gfb, blk, \
-                               0, s, a, ep, start, nb);                    \
-          else                                                             \
-            hipLaunchKernelGGL((nb_train_fb_kernel<KT1_, false>), gfb, blk,\
-                               0, s, a, ep, start, nb);                    \
-          break;
-        NB_CASE(1) NB_CASE(2) NB_CASE(3) NB_CASE(4) NB_CASE(5)
-        NB_CASE(6) NB_CASE(7) NB_CASE(8) NB_CASE(9)
-#undef NB_CASE
-        default: nb_set_error("n_dim unsupported"); return NB_ERR_UNSUPPORTED;
+      if (!NB_LAUNCH_KT1_LARGE(nb_train_fb_kernel, t->kt1, t->large, gfb, blk,
+                               0, s, a, ep, start, nb)) {
+        nb_set_error("n_dim unsupported");
+        return NB_ERR_UNSUPPORTED;
       }
       if (t->large)
         hipLaunchKernelGGL(nb_train_g_kernel<true>, gg, blk, 0, s, a, nb,
@@ -2525,29 +2397,16 @@ int nb_trainer_run_fleet(nb_trainer* t, const int32_t* const* perm_dev_of,
 
 int nb_trainer_status(nb_trainer* t, int32_t* status_host, void* stream) {
   NB_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-  if (!t->two_launch) {
-    int sync[SYNC_INTS];
+  int sync[SYNC_INTS];
+  if (!t->two_launch)
     NB_HIP_CHECK(hipMemcpy(sync, t->sync_dev, sizeof sync,
                            hipMemcpyDeviceToHost));
-    for (int i = 0; i < t->E; ++i)
-      if (sync[SYNC_WORDS * i + 1] != 0) {
-        nb_set_error("resident training kernel failed for network %d (%s); "
-                     "set NB_TRAIN_TWO_LAUNCH=1 to train with two launches "
-                     "per step", i,
-                     sync[SYNC_WORDS * i + 1] == 2
-                         ? "its workgroups do not share an XCD"
-                         : "barrier timeout");
-        return NB_ERR_HIP;
-      }
-  }
-  for (int i = 0; i < t->E; ++i) {
-    double scal[8];
-    NB_HIP_CHECK(hipMemcpy(scal, t->nets_host[i].scal, sizeof scal,
-                           hipMemcpyDeviceToHost));
-    const int n_iter = (int)scal[3];
-    status_host[i] = (scal[4] != 0.0) ? -n_iter : n_iter;
-  }
-  return NB_OK;
+  std::vector<double> scal((size_t)t->E * 8);
+  for (int i = 0; i < t->E; ++i)
+    NB_HIP_CHECK(hipMemcpy(&scal[8 * (size_t)i], t->nets_host[i].scal,
+                           8 * sizeof(double), hipMemcpyDeviceToHost));
+  return chunk_status(t, t->two_launch ? nullptr : sync, scal.data(),
+                      status_host);
 }
 
 int nb_trainer_run_async(nb_trainer* t, const int32_t* const* perm_dev_of,
@@ -2591,25 +2450,9 @@ int nb_trainer_wait(nb_trainer* t, int64_t ticket, int32_t* status_host) {
   }
   const int slot = (int)(ticket % nb_trainer::RING);
   NB_HIP_CHECK(hipEventSynchronize(t->ring_event[slot]));
-  if (!t->two_launch) {
-    const int* sync = t->pin_sync + (size_t)slot * SYNC_INTS;
-    for (int i = 0; i < t->E; ++i)
-      if (sync[SYNC_WORDS * i + 1] != 0) {
-        nb_set_error("resident training kernel failed for network %d (%s); "
-                     "set NB_TRAIN_TWO_LAUNCH=1 to train with two launches "
-                     "per step", i,
-                     sync[SYNC_WORDS * i + 1] == 2
-                         ? "its workgroups do not share an XCD"
-                         : "barrier timeout");
-        return NB_ERR_HIP;
-      }
-  }
-  const double* scal = t->pin_scal + (size_t)slot * t->E * 8;
-  for (int i = 0; i < t->E; ++i) {
-    const int n_iter = (int)scal[8 * i + 3];
-    status_host[i] = (scal[8 * i + 4] != 0.0) ? -n_iter : n_iter;
-  }
-  return NB_OK;
+  return chunk_status(
+      t, t->two_launch ? nullptr : t->pin_sync + (size_t)slot * SYNC_INTS,
+      t->pin_scal + (size_t)slot * t->E * 8, status_host);
 }
 
 int nb_trainer_loss_curve(nb_trainer* t, int32_t net, double* out_host,
@@ -2627,22 +2470,7 @@ int nb_trainer_weights(nb_trainer* t, int32_t net, double* const* coefs,
   std::vector<double> w((size_t)t->n_w);
   NB_HIP_CHECK(hipMemcpy(w.data(), t->nets_host[net].W,
                          (size_t)t->n_w * sizeof(double), hipMemcpyDeviceToHost));
-  const int D = t->n_dim;
-  const double* w1 = w.data();
-  const double* w2 = w1 + (size_t)t->kt1 * NB_HT1 * NB_TILE;
-  const double* w3 = w2 + (size_t)NB_HT1 * NB_HT2 * NB_TILE;
-  const double* w4 = w3 + (size_t)NB_HT2 * NB_HT3 * NB_TILE;
-  for (int k = 0; k < D; ++k)
-    for (int h = 0; h < NB_H1; ++h) coefs[0][(size_t)k * NB_H1 + h] = get_w(w1, NB_HT1, k, h);
-  for (int h = 0; h < NB_H1; ++h) icpts[0][h] = get_w(w1, NB_HT1, D, h);
-  for (int k = 0; k < NB_H1; ++k)
-    for (int h = 0; h < NB_H2; ++h) coefs[1][(size_t)k * NB_H2 + h] = get_w(w2, NB_HT2, k, h);
-  for (int h = 0; h < NB_H2; ++h) icpts[1][h] = get_w(w2, NB_HT2, NB_H1, h);
-  for (int k = 0; k < NB_H2; ++k)
-    for (int h = 0; h < NB_H3; ++h) coefs[2][(size_t)k * NB_H3 + h] = get_w(w3, NB_HT3, k, h);
-  for (int h = 0; h < NB_H3; ++h) icpts[2][h] = get_w(w3, NB_HT3, NB_H2, h);
-  for (int k = 0; k < NB_H3; ++k) coefs[3][k] = get_w(w4, 1, k, 0);
-  icpts[3][0] = get_w(w4, 1, NB_H3, 0);
+  unpack_network(t->n_dim, t->kt1, w.data(), coefs, icpts);
   return NB_OK;
 }
 

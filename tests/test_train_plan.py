@@ -1,0 +1,193 @@
+"""The host arithmetic of the emulator trainer (nautilus_amd/csrc/
+nb_train_plan.h, the very header nb_mlp_train.hip includes), built for the
+host by tests/train_plan_check.cpp: which workgroup updates which weight tile
+in the gradient phase, and where a weight lives in the tile-major buffers.
+
+``g_job`` of the trainer has a body for five block shapes and runs a record
+of any other shape as 1 x 1, leaving tiles without their Adam step: the
+planner must emit only those shapes and cover every tile exactly once."""
+
+import json
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.abspath(os.path.dirname(__file__)))
+GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'train_plan.json')
+
+H = (100, 50, 20, 1)                     # outputs of the four layers
+HT = (7, 4, 2, 1)                        # ... in 16-wide tiles
+SHAPES = {(1, 1), (2, 1), (1, 2), (3, 1), (2, 2)}    # (nk, nh) g_job runs
+XCD_SLOTS, G_ROWT = 32, 13
+# the slots nb_trainer_create_fleet checks the lists against (bytes)
+JOBS_SLOT, SCHED_SLOT = 14336 - 13312, 32768 - 14336
+
+
+def layer_tiles(kt1):
+    """(k-tiles, h-tiles) of the four layers"""
+    return list(zip((kt1,) + HT[:3], HT))
+
+
+@pytest.fixture(scope='module')
+def exe(tmp_path_factory):
+    cxx = next((c for c in ('g++', 'c++', 'clang++', 'hipcc')
+                if shutil.which(c)), None)
+    assert cxx is not None, 'no C++ compiler (the build needs hipcc anyway)'
+    path = str(tmp_path_factory.mktemp('train_plan') / 'train_plan_check')
+    subprocess.check_call(
+        [cxx, '-x', 'c++', '-std=c++17', '-O2',
+         '-I', os.path.join(ROOT, 'nautilus_amd', 'csrc'),
+         os.path.join(ROOT, 'tests', 'train_plan_check.cpp'), '-o', path])
+    return path
+
+
+@pytest.fixture(scope='module')
+def golden():
+    with open(GOLDEN) as f:
+        return json.load(f)
+
+
+@pytest.fixture(scope='module')
+def planned(exe, golden):
+    """the program's output in the form of the golden file"""
+    forced = []
+    for p in golden['plans']:
+        pair = (p['late_only'], p['shape'])
+        if pair != (-1, -1) and pair not in forced:
+            forced.append(pair)
+    out = subprocess.check_output(
+        [exe, 'plan'] + [str(v) for pair in forced for v in pair], text=True)
+    rounds, plans = {}, {}
+    for line in out.splitlines():
+        f = line.split()
+        if f[0] == 'rounds':
+            rounds[f[1]] = [int(v) for v in f[2:]]
+        else:
+            key = tuple(int(v) for v in f[1:4])
+            plans.setdefault(key, {})[f[0]] = [int(v) for v in f[4:]]
+    return {'rounds': rounds,
+            'plans': [dict(kt1=k[0], late_only=k[1], shape=k[2], **v)
+                      for k, v in plans.items()]}
+
+
+def records(ints):
+    assert len(ints) % 5 == 0
+    return [tuple(ints[i:i + 5]) for i in range(0, len(ints), 5)]
+
+
+def chosen(planned, kt1):
+    """jobs and schedule of g_plan(kt1, -1, -1)"""
+    p, = [p for p in planned['plans']
+          if (p['kt1'], p['late_only'], p['shape']) == (kt1, -1, -1)]
+    return records(p['jobs']), p['sched']
+
+
+def check_jobs(jobs, kt1):
+    """coverage and shapes of one job list"""
+    cover = [np.zeros(t, dtype=int) for t in layer_tiles(kt1)]
+    for layer, kt0, nk, ht0, nh in jobs:
+        assert 0 <= layer < 4
+        assert (nk, nh) in SHAPES, (kt1, layer, nk, nh)
+        kt_n, ht_n = cover[layer].shape
+        assert 0 <= kt0 and kt0 + nk <= kt_n, (kt1, layer, kt0, nk)
+        assert 0 <= ht0 and ht0 + nh <= ht_n, (kt1, layer, ht0, nh)
+        cover[layer][kt0:kt0 + nk, ht0:ht0 + nh] += 1
+    assert sum(c.size for c in cover) == 45 + 7 * (kt1 - 1)
+    for layer, c in enumerate(cover):
+        assert (c == 1).all(), (kt1, layer, c)
+
+
+@pytest.mark.parametrize('kt1', range(1, 10))
+def test_every_tile_has_one_job_of_a_shape_g_job_runs(planned, kt1):
+    rounds = records(planned['rounds'][str(kt1)])
+    check_jobs(rounds, kt1)
+    assert len(rounds) <= 32                 # two rounds of 16 workgroups
+    assert 4 * 5 * len(rounds) <= JOBS_SLOT
+    check_jobs(chosen(planned, kt1)[0], kt1)
+
+
+@pytest.mark.parametrize('kt1', range(1, 10))
+def test_schedule(planned, kt1):
+    jobs, sched = chosen(planned, kt1)
+    assert len(sched) == 2 * XCD_SLOTS
+    early, late = sched[0::2], sched[1::2]
+    assert sorted(j for j in early + late if j >= 0) == list(range(len(jobs)))
+    assert all(j == -1 for j in early[:G_ROWT])   # these run FB meanwhile
+    assert all(jobs[j][0] in (1, 2, 3) for j in early if j >= 0)
+    assert all(jobs[j][0] == 0 for j in late if j >= 0)
+    assert all(j >= -1 for j in sched)
+    # [schedule][its job records] in one slot
+    assert 4 * (len(sched) + 5 * len(jobs)) <= SCHED_SLOT
+
+
+def test_job_counts(planned):
+    """the figures of the planner this one was moved from, built on its own"""
+    plan = [chosen(planned, kt1) for kt1 in range(1, 10)]
+    n_early = [sum(j >= 0 for j in s[0::2]) for _, s in plan]
+    n_late = [sum(j >= 0 for j in s[1::2]) for _, s in plan]
+    assert [len(j) for j, _ in plan] == [26, 32, 31, 32, 41, 48, 42, 49, 45]
+    assert n_early == [19, 18, 19, 18, 19, 19, 19, 19, 19]
+    assert n_late == [7, 14, 12, 14, 22, 29, 23, 30, 26]
+    assert [len(records(planned['rounds'][str(k)])) for k in range(1, 10)] == \
+        [24, 24, 31, 31, 29, 29, 27, 27, 31]
+
+
+def test_planner_is_the_recorded_one(planned, golden):
+    """Bit for bit what the planner gave before it moved to the header, for
+    kt1 1 .. 9: unforced, and with (late_only, shape) forced -- then through
+    the NB_TRAIN_LATE_ONLY / NB_TRAIN_LATE_SHAPE switches, now through the
+    arguments of g_plan (pairs of profiles/r06/train_plan_sweep.txt, and each
+    of the two forced alone; a pair no plan exists for gives empty lists)."""
+    assert len(golden['plans']) == 9 * 6
+    assert sorted(planned['rounds']) == sorted(golden['rounds'])
+    assert planned['rounds'] == golden['rounds']
+    key = lambda p: (p['kt1'], p['late_only'], p['shape'])
+    assert sorted(map(key, planned['plans'])) == \
+        sorted(map(key, golden['plans']))
+    want = {key(p): p for p in golden['plans']}
+    for p in planned['plans']:
+        assert p == want[key(p)], key(p)
+
+
+def tile_index(c, r):
+    # element (c, r) of a 16 x 16 tile (nb_train_plan.h, written out again)
+    return ((c // 8) * 64 + ((c // 2) % 4) * 16 + r) * 2 + c % 2
+
+
+@pytest.mark.parametrize('n_dim, kt1', [(1, 1), (15, 1), (16, 2), (50, 4),
+                                        (128, 9)])
+def test_pack_network(exe, tmp_path, n_dim, kt1):
+    subprocess.check_call([exe, 'pack', str(n_dim), str(tmp_path)])
+    w, wt, back = (np.fromfile(str(tmp_path / name)) for name in
+                   ('w.bin', 'wt.bin', 'back.bin'))
+    tiles = layer_tiles(kt1)
+    assert w.size == 256 * sum(k * h for k, h in tiles)
+    assert wt.size == 256 * sum(k * h for k, h in tiles[1:])
+    rows = (n_dim,) + H[:3]
+    # weight_value of the program; the bias is row k = rows
+    value = [(l + 1) * 100000.0 + 1000.0 * np.arange(rows[l] + 1)[:, None] +
+             np.arange(H[l])[None, :] + 0.25 for l in range(4)]
+    # unpack(pack(w)) == w: coefficients, then intercepts, layer by layer
+    assert np.array_equal(
+        back, np.concatenate([v.ravel() for v in value]))
+    want, want_t = np.zeros_like(w), np.zeros_like(wt)
+    off = off_t = 0
+    for l, (kt_n, ht_n) in enumerate(tiles):
+        k, h = np.indices(value[l].shape)
+        at = ((k >> 4) * ht_n + (h >> 4)) * 256 + tile_index(k & 15, h & 15)
+        assert len(np.unique(at)) == at.size and at.max() < 256 * kt_n * ht_n
+        want[off + at] = value[l]
+        off += 256 * kt_n * ht_n
+        if l > 0:
+            # tile [h >> 4][k >> 4], element (h & 15, k & 15)
+            at = ((h >> 4) * kt_n + (k >> 4)) * 256 + \
+                tile_index(h & 15, k & 15)
+            assert len(np.unique(at)) == at.size
+            want_t[off_t + at] = value[l]
+            off_t += 256 * kt_n * ht_n
+    # every weight and bias at its place, 0.0 everywhere else
+    assert np.array_equal(w, want)
+    assert np.array_equal(wt, want_t)
