@@ -36,6 +36,7 @@
 #include <limits.h>
 
 #include "nb_common.h"
+#include "nb_launch.h"
 
 #include "nb_tile.h"
 

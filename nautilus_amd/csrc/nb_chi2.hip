@@ -39,6 +39,7 @@
 //
 // The diagonal case (sigma) is a separate memory-bound kernel below.
 #include "nb_common.h"
+#include "nb_launch.h"
 #include "nb_lds_copy.h"
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)

@@ -42,6 +42,7 @@
 // algorithmic at D = 50 (0.56 of the fp64 MFMA peak), HBM traffic 1.02x
 // algorithmic.
 #include "nb_common.h"
+#include "nb_launch.h"
 
 #include <cstdlib>
 
@@ -440,7 +441,7 @@ nb_eval_kernel(EvalArgs a, int w_doubles) {
 
         // unit-cube limits of slot (ks, lg) = feature 8 (ks >> 1) + 2 lg +
         // (ks & 1): [0, 1) for the features of a bound clipped to the cube,
-        // unbounded otherwise (what nb_api.hip stores at off_ulo / off_uhi;
+        // unbounded otherwise (what nb_pack.h stores at off_ulo / off_uhi;
         // computed here, the loads were serialised by the compiler)
         bool cbad[TPW];
 #pragma unroll
@@ -906,7 +907,7 @@ static unsigned long long* g_eval_counters = nullptr;
 void nb_eval_set_counters(unsigned long long* dev) { g_eval_counters = dev; }
 unsigned long long* nb_eval_counters() { return g_eval_counters; }
 
-// host entry used by nb_api.cpp
+// host entry used by nb_api.hip
 int nb_launch_eval(int dt, const double* const* blobs_dev, int nb, int mode,
                    const double* x, long long n, unsigned char* out_u8,
                    int* out_i32, double* out_f64, unsigned long long seed,

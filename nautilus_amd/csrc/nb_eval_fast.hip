@@ -33,6 +33,7 @@
 // with at most one outer member or MODE_SCORE; everything else goes through
 // nb_eval.hip.
 #include "nb_common.h"
+#include "nb_launch.h"
 
 #include <type_traits>
 

@@ -47,6 +47,7 @@
 // skipped.  A finite sum that overflows is NaN by the same rule, as in the
 // numpy twin.
 #include "nb_common.h"
+#include "nb_launch.h"
 #include "nb_lds_copy.h"
 #include "nb_poisson_term.h"
 

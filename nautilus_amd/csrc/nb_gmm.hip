@@ -33,6 +33,7 @@
 // the restart.  Everything is deterministic (fixed reduction orders, Philox
 // for the seeding).
 #include "nb_sym.h"
+#include "../../include/nautilus_hip.h"
 
 #include <atomic>
 #include <cstdlib>
@@ -815,23 +816,31 @@ int launch_gmm(const GmmArgs& a, int wgs, hipStream_t stream) {
 
 }  // namespace
 
-long long nb_gmm_out_stride_impl(int d) { return 6 + 2LL * d + 2LL * d * d; }
-long long nb_gmm_scratch_stride_impl(long long n, int d) {
+// ---- the exports (include/nautilus_hip.h) ----------------------------------
+extern "C" {
+
+int64_t nb_gmm_out_doubles(int32_t d) { return 6 + 2LL * d + 2LL * d * d; }
+int64_t nb_gmm_scratch_doubles(int64_t n, int32_t d) {
   return gm_layout(n, d).total;
 }
 // [n_init restarts][counter blocks of the restarts]
-long long nb_gmm_work_doubles_impl(long long n, int d, int n_init) {
-  return (long long)n_init * (nb_gmm_scratch_stride_impl(n, d) +
+int64_t nb_gmm_work_doubles(int64_t n, int32_t d, int32_t n_init) {
+  return (long long)n_init * (nb_gmm_scratch_doubles(n, d) +
                               GM_SYNC_INTS / 2) + 16;
 }
-long long nb_gmm_logp_offset_impl(long long n, int d) {
-  return gm_layout(n, d).lp0;
+int64_t nb_gmm_logp_offset(int32_t d) {
+  return gm_layout(2, d).lp0;                   // (does not depend on n)
 }
 
-int nb_launch_gmm(const double* x, long long n, int d, int n_init,
-                  unsigned long long seed, double tol, double reg, int max_iter,
-                  const int* init_labels, double* out, double* scratch,
-                  hipStream_t stream) {
+int nb_gmm_fit(const double* x, int64_t n, int32_t d, int32_t n_init,
+               uint64_t seed, double tol, double reg, int32_t max_iter,
+               const int32_t* init_labels, double* out, double* scratch,
+               void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (x == nullptr || out == nullptr || scratch == nullptr) {
+    nb_set_error("null argument");
+    return NB_ERR_ARG;
+  }
   if (d < 1 || d > 128) {
     nb_set_error("device mixture fit supports n_dim <= 128 (got %d)", d);
     return NB_ERR_UNSUPPORTED;
@@ -844,8 +853,8 @@ int nb_launch_gmm(const double* x, long long n, int d, int n_init,
   a.x = x; a.n = (int)n; a.d = d; a.n_init = n_init; a.seed = seed;
   a.tol = tol; a.reg = reg; a.max_iter = max_iter; a.init_labels = init_labels;
   a.out = out; a.scratch = scratch;
-  a.out_stride = nb_gmm_out_stride_impl(d);
-  a.scratch_stride = nb_gmm_scratch_stride_impl(n, d);
+  a.out_stride = nb_gmm_out_doubles(d);
+  a.scratch_stride = nb_gmm_scratch_doubles(n, d);
   a.sync = (int*)(scratch + (long long)n_init * a.scratch_stride);
   NB_HIP_CHECK(hipMemsetAsync(a.sync, 0,
                               (size_t)n_init * GM_SYNC_INTS * sizeof(int),
@@ -868,7 +877,9 @@ int nb_launch_gmm(const double* x, long long n, int d, int n_init,
   return NB_OK;
 }
 
-int nb_gmm_set_cap_impl(int max_wgs) {
+int nb_gmm_set_max_wgs(int32_t max_wgs) {
   g_gmm_cap.store(max_wgs < 0 ? 0 : max_wgs, std::memory_order_relaxed);
   return NB_OK;
 }
+
+}  // extern "C"

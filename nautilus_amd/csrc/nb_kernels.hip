@@ -1,5 +1,7 @@
 // Proposal draw, stream compaction, shell statistics and small helpers.
 #include "nb_common.h"
+#include "nb_launch.h"
+#include "../../include/nautilus_hip.h"
 
 #include "nb_draw.h"
 
@@ -454,13 +456,31 @@ int nb_launch_draw(const double* blob_dev, int n_dim, unsigned long long seed,
   return NB_OK;
 }
 
-long long nb_compact_chunks(long long n) { return (n + CHUNK - 1) / CHUNK; }
+// ---- exports that need no handle (include/nautilus_hip.h) ------------------
+static long long nb_compact_chunks(long long n) {
+  return (n + CHUNK - 1) / CHUNK;
+}
+static int nb_lse_blocks(long long n) {
+  long long b = (n + 255) / 256;
+  if (b > 1024) b = 1024;
+  if (b < 1) b = 1;
+  return (int)b;
+}
 
-int nb_launch_compact(const double* x, const unsigned char* flags,
-                      unsigned char mask, unsigned char flip, long long n,
-                      int n_dim, double* out,
-                      long long* src_idx, long long* counts,
-                      long long* chunk_counts, hipStream_t stream) {
+extern "C" {
+
+int64_t nb_compact_scratch_bytes(int64_t n) {
+  return (nb_compact_chunks(n) * 2 + 2) * (int64_t)sizeof(long long);
+}
+
+int nb_compact_rows(const double* x, const uint8_t* flags, uint8_t mask,
+                    uint8_t flip, int64_t n, int32_t n_dim, double* out,
+                    int64_t* src_idx_out, int64_t* counts_out, void* scratch,
+                    void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  long long* src_idx = (long long*)src_idx_out;
+  long long* counts = (long long*)counts_out;
+  long long* chunk_counts = (long long*)scratch;
   const long long n_chunks = nb_compact_chunks(n);
   if (n_chunks == 0) {
     NB_HIP_CHECK(hipMemsetAsync(counts, 0, 2 * sizeof(long long), stream));
@@ -479,15 +499,14 @@ int nb_launch_compact(const double* x, const unsigned char* flags,
   return NB_OK;
 }
 
-int nb_lse_blocks(long long n) {
-  long long b = (n + 255) / 256;
-  if (b > 1024) b = 1024;
-  if (b < 1) b = 1;
-  return (int)b;
+int64_t nb_shell_stats_scratch_bytes(int64_t n) {
+  return (int64_t)nb_lse_blocks(n) * 4 * sizeof(double);
 }
 
-int nb_launch_shell_stats(const double* log_l, long long n, double threshold,
-                          double* out, double* partial, hipStream_t stream) {
+int nb_shell_stats(const double* log_l, int64_t n, double threshold,
+                   double* out, void* scratch, void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  double* partial = (double*)scratch;
   const int blocks = nb_lse_blocks(n);
   hipLaunchKernelGGL(nb_lse_partial_kernel, dim3(blocks), dim3(256), 0,
                      stream, log_l, n, threshold, partial);
@@ -497,9 +516,9 @@ int nb_launch_shell_stats(const double* log_l, long long n, double threshold,
   return NB_OK;
 }
 
-int nb_launch_philox(unsigned long long seed, unsigned long long offset,
-                     unsigned block, unsigned tag, long long n, double* u,
-                     hipStream_t stream) {
+int nb_philox_uniform(uint64_t seed, uint64_t offset, uint32_t block,
+                      uint32_t tag, int64_t n, double* u, void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
   if (n <= 0) return NB_OK;
   hipLaunchKernelGGL(nb_philox_kernel, dim3((unsigned)((n + 255) / 256)),
                      dim3(256), 0, stream, seed, offset, block, tag, n, u);
@@ -507,7 +526,7 @@ int nb_launch_philox(unsigned long long seed, unsigned long long offset,
   return NB_OK;
 }
 
-int nb_run_mfma_peak(int iters, double* tflops) {
+int nb_mfma_f64_peak(int32_t iters, double* tflops) {
   double* sink = nullptr;
   NB_HIP_CHECK(hipMalloc(&sink, 8));
   hipEvent_t e0, e1;
@@ -532,6 +551,8 @@ int nb_run_mfma_peak(int iters, double* tflops) {
   (void)hipFree(sink);
   return NB_OK;
 }
+
+}  // extern "C"
 
 // ---------------------------------------------------------------------------
 // PhaseShift.transform (bounds/periodic.py:50-72), in place.  numpy's
@@ -559,12 +580,27 @@ nb_phase_shift_kernel(double* __restrict__ x, long long total, int n_dim,
 }
 }  // namespace
 
-int nb_launch_phase_shift(double* x, long long n, int n_dim, const double* s,
-                          const unsigned char* on, int inverse,
-                          hipStream_t stream) {
-  ShiftArgs a;
-  for (int i = 0; i < 16 * NB_MAX_DT; ++i) { a.s[i] = s[i]; a.on[i] = on[i]; }
-  const long long total = n * n_dim;
+extern "C" int nb_phase_shift(double* x, int64_t n, int32_t n_dim,
+                              int32_t n_periodic, const int32_t* periodic,
+                              const double* centers, int32_t inverse,
+                              void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (n_dim < 1 || n_dim > 16 * NB_MAX_DT || n_periodic < 0 ||
+      (n_periodic > 0 && (periodic == nullptr || centers == nullptr))) {
+    nb_set_error("bad phase shift arguments");
+    return NB_ERR_ARG;
+  }
+  ShiftArgs a = {};
+  for (int i = 0; i < n_periodic; ++i) {
+    if (periodic[i] < 0 || periodic[i] >= n_dim) {
+      nb_set_error("periodic index %d out of range", periodic[i]);
+      return NB_ERR_ARG;
+    }
+    a.s[periodic[i]] = -centers[i] + 0.5;
+    a.on[periodic[i]] = 1;
+  }
+  if (n <= 0 || n_periodic == 0) return NB_OK;
+  const long long total = (long long)n * n_dim;
   long long blocks = (total + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(nb_phase_shift_kernel, dim3((unsigned)blocks), dim3(256),

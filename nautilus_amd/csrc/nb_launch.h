@@ -1,0 +1,70 @@
+// Launchers and size functions that cross a file boundary: defined beside
+// their kernels, called from nb_api.hip (or another kernel file).  The caller
+// and the defining file both include this header, so a signature that drifts
+// is a compile error.
+#pragma once
+
+#include "nb_common.h"
+
+bool nb_eval_fast_eligible(int n_dim, int K, int M, int E, bool sample);
+int nb_launch_eval_fast(const double* blob_dev, int n_dim, bool sample, int m,
+                        int recentre, const double* x, const long long* idx,
+                        long long n,
+                        unsigned char* out_u8, double* out_f64,
+                        unsigned long long seed, unsigned long long offset,
+                        hipStream_t stream);
+int nb_launch_cand(int dt, int n_dim, const double* const* blobs_dev,
+                   const int* group_base_dev, int nb, int n_groups, int b_off,
+                   int g_off, int accumulate, int mode, const double* x,
+                   long long n, unsigned char* st, int* first, int* work,
+                   unsigned long long seed, unsigned long long offset,
+                   int** dense_out, int** totals_out, long long* n_pad_out,
+                   hipStream_t stream);
+long long nb_cand_work_bytes(int dt, int mode, long long n, int n_groups);
+int nb_launch_eval_fast_batch(const double* blob0_dev, int n_dim, int recentre,
+                              const double* x, const void* groups_dev,
+                              int n_groups, const int* totals_dev,
+                              const int* dense_dev, long long n_pad,
+                              long long n_upper, int out_mode,
+                              unsigned char* st, int* first,
+                              hipStream_t stream);
+int nb_launch_eval(int dt, const double* const* blobs_dev, int nb, int mode,
+                   const double* x, long long n, unsigned char* out_u8,
+                   int* out_i32, double* out_f64, unsigned long long seed,
+                   unsigned long long offset, hipStream_t stream);
+void nb_eval_set_counters(unsigned long long* dev);
+int nb_launch_draw(const double* blob_dev, int n_dim, unsigned long long seed,
+                   unsigned long long offset, long long n, double* x_out,
+                   hipStream_t stream);
+int nb_launch_transform(const double* ell_block, int dt, int n_dim,
+                        const double* x, long long n, double* y,
+                        hipStream_t stream);
+int nb_launch_standardize(const double* x, long long n, int d, double* mean,
+                          double* scale, double* out, hipStream_t stream);
+int nb_launch_prior_table(const double* u, long long n, int d,
+                          const double* par, const unsigned char* kind,
+                          int n_keys, const int* key_column,
+                          const double* key_value, int column_major,
+                          int level, double* out, hipStream_t stream);
+int nb_launch_ell_stream(const double* cvec, const double* binv, int n_dim,
+                         const double* x, long long n, unsigned char* mask,
+                         hipStream_t stream);
+int nb_launch_mixture(const double* blob, int n_dim, int n_comp,
+                      const double* x, long long n, double* out, int* label,
+                      hipStream_t stream);
+int nb_launch_chi2(const double* blob, int n_data, const double* model,
+                   long long ld, long long n, double log_norm, double* out,
+                   hipStream_t stream);
+int nb_launch_chi2_diag(const double* blob, int n_data, const double* model,
+                        long long ld, long long n, double log_norm,
+                        double* out, hipStream_t stream);
+int nb_launch_poisson(const double* tab, int n_data, const double* model,
+                      long long ld, long long n, double log_const,
+                      double* out, hipStream_t stream);
+int nb_launch_noise(const double* tab, int n_data, int mode,
+                    const double* model, long long ld, const double* noise,
+                    long long ld_noise, long long n, double log_norm,
+                    double* out, hipStream_t stream);
+int nb_launch_fold_poisson(const double* blob, int n_data, int n_src,
+                           const double* src, long long ld, long long n,
+                           double log_const, double* out, hipStream_t stream);

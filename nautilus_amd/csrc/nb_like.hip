@@ -6,6 +6,7 @@
 // load instruction of a wavefront covers 4 points x 128 contiguous bytes, the
 // per-point sum is a 4-step shuffle reduction.
 #include "nb_common.h"
+#include "../../include/nautilus_hip.h"
 
 namespace {
 
@@ -75,8 +76,16 @@ inline unsigned like_blocks(long long n) {
 
 }  // namespace
 
-int nb_launch_rosenbrock(const double* u, long long n, int d, double lo,
-                         double hi, double a, double* out, hipStream_t stream) {
+// ---- the exports (include/nautilus_hip.h) ----------------------------------
+extern "C" {
+
+int nb_loglike_rosenbrock(const double* u, int64_t n, int32_t d, double lo,
+                          double hi, double a, double* out, void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (d < 2 || (n > 0 && (u == nullptr || out == nullptr))) {
+    nb_set_error("bad Rosenbrock likelihood arguments");
+    return NB_ERR_ARG;
+  }
   if (n <= 0) return NB_OK;
   hipLaunchKernelGGL(nb_rosenbrock_kernel, dim3(like_blocks(n)), dim3(256), 0,
                      stream, u, n, d, lo, hi - lo, a, out);
@@ -84,11 +93,20 @@ int nb_launch_rosenbrock(const double* u, long long n, int d, double lo,
   return NB_OK;
 }
 
-int nb_launch_funnel(const double* u, long long n, int d, double mu, double s0,
-                     double k, double c, double* out, hipStream_t stream) {
+int nb_loglike_funnel(const double* u, int64_t n, int32_t d, double mu,
+                      double s0, double k, double c, double* out,
+                      void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (d < 2 || !(s0 > 0.0) || !(c > 0.0) ||
+      (n > 0 && (u == nullptr || out == nullptr))) {
+    nb_set_error("bad funnel likelihood arguments");
+    return NB_ERR_ARG;
+  }
   if (n <= 0) return NB_OK;
   hipLaunchKernelGGL(nb_funnel_kernel, dim3(like_blocks(n)), dim3(256), 0,
                      stream, u, n, d, mu, s0, k, c, out);
   NB_HIP_CHECK(hipGetLastError());
   return NB_OK;
 }
+
+}  // extern "C"

@@ -8,6 +8,7 @@
 // ever rises, so the pool stays at n_live + one batch.  The per-shell sums
 // over the live points are wavefront-shuffle reductions (nb_live_stats).
 #include "nb_common.h"
+#include "../../include/nautilus_hip.h"
 
 namespace {
 
@@ -156,9 +157,18 @@ nb_live_stats_kernel(const double* __restrict__ ll, long long n,
 
 }  // namespace
 
-int nb_launch_live_append(const double* ll, long long n, const double* thr,
-                          double* pool, int* pool_n, int cap, int* overflow,
-                          hipStream_t stream) {
+// ---- the exports (include/nautilus_hip.h) ----------------------------------
+extern "C" {
+
+int nb_live_append(const double* ll, int64_t n, const double* thr,
+                   double* pool, int32_t* pool_n, int32_t cap,
+                   int32_t* overflow, void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (cap < 1 || thr == nullptr || pool == nullptr || pool_n == nullptr ||
+      overflow == nullptr || (n > 0 && ll == nullptr)) {
+    nb_set_error("bad live-pool arguments");
+    return NB_ERR_ARG;
+  }
   if (n <= 0) return NB_OK;
   long long blocks = (n + 255) / 256;
   if (blocks > 1024) blocks = 1024;
@@ -168,19 +178,33 @@ int nb_launch_live_append(const double* ll, long long n, const double* thr,
   return NB_OK;
 }
 
-int nb_launch_live_select(const double* pool, const int* pool_n, int cap,
-                          int k, double* out, int* out_n, double* thr,
-                          double* stats, hipStream_t stream) {
+int nb_live_select(const double* pool, const int32_t* pool_n, int32_t cap,
+                   int32_t k, double* out, int32_t* out_n, double* thr,
+                   double* stats, void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (cap < 1 || k < 1 || pool == nullptr || pool_n == nullptr ||
+      out == nullptr || out_n == nullptr || thr == nullptr ||
+      stats == nullptr) {
+    nb_set_error("bad live-pool arguments");
+    return NB_ERR_ARG;
+  }
   hipLaunchKernelGGL(nb_live_select_kernel, dim3(1), dim3(LV_THREADS), 0,
                      stream, pool, pool_n, cap, k, out, out_n, thr, stats);
   NB_HIP_CHECK(hipGetLastError());
   return NB_OK;
 }
 
-int nb_launch_live_stats(const double* ll, long long n, const double* thr,
-                         double* out, hipStream_t stream) {
+int nb_live_stats(const double* ll, int64_t n, const double* thr, double* out,
+                  void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (thr == nullptr || out == nullptr || (n > 0 && ll == nullptr)) {
+    nb_set_error("null argument");
+    return NB_ERR_ARG;
+  }
   hipLaunchKernelGGL(nb_live_stats_kernel, dim3(1), dim3(1024), 0, stream, ll,
                      n, thr, out);
   NB_HIP_CHECK(hipGetLastError());
   return NB_OK;
 }
+
+}  // extern "C"

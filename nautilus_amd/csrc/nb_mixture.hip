@@ -12,7 +12,7 @@
 //    the pair loads and the permuted K order of nb_stream.hip, and kept raw.
 //    Per component the centred operand d = x - mu_k is formed in registers
 //    (mu_k from LDS, 4 distinct 16-byte addresses per read);
-//  * a component is one record of the blob (nb_common.h,
+//  * a component is one record of the blob (nb_layout.h,
 //    nb_mixture_record): its lower-triangular
 //    L_k^-1 as K-permuted 16x16 tiles, mu_k zero padded to 16 DT, a_k.  Where
 //    all K records fit the LDS of a CU they are copied once per workgroup and
@@ -26,6 +26,7 @@
 //    (max, sum scaled by exp(-max)) pair in fp64, so no K-wide array of terms
 //    exists anywhere.  The label is the first k that attains the maximum.
 #include "nb_common.h"
+#include "nb_launch.h"
 #include "nb_quadform.h"
 
 #include <cfloat>
@@ -307,7 +308,7 @@ int launch(const double* blob, int n_dim, int n_comp, const double* x,
 
 }  // namespace
 
-// blob: n_comp records of nb_mixture_record(DT) doubles (nb_api.hip,
+// blob: n_comp records of nb_mixture_record(DT) doubles (nb_pack.h,
 // nb_mixture_create): DT(DT+1)/2 lower-triangular 16x16 tiles of
 // W[k][h] = L^-1[h][k] with the K permutation of nb_stream.hip, then mu zero
 // padded to 16 DT, then a_k.

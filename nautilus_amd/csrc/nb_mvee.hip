@@ -40,8 +40,11 @@
 // Centre, covariance and the final scaling (basic.py:233-241) follow from u
 // with one more nb_moments launch and one "B only" call (nb_quadform_max).
 #include "nb_sym.h"
+#include "nb_launch.h"
+#include "../../include/nautilus_hip.h"
 
 #include <cstring>
+#include <vector>
 
 namespace {
 
@@ -686,7 +689,7 @@ nb_spd_inverse_kernel(MomBatch batch, int d, int vw, int nt) {
 // moments) = L D L^T by elimination on the packed lower triangles of [C | I]
 // in LDS (one barrier per pivot), W = D^-1/2 L^-1.  Written twice: row-major
 // (for the host's back transformation) and as the operand block of
-// nb_transform_kernel (nb_common.h "ell block", centre 0), which maps the
+// nb_transform_kernel (nb_layout.h "ell block", centre 0), which maps the
 // points to unit covariance.  Near-singular pivots are clamped.
 constexpr int MV_WH_EPT = 17;          // ceil(128 * 129 / 2 / 512)
 
@@ -877,22 +880,29 @@ inline long long mv_prob_doubles(long long n_max, int d, int nsc) {
 
 }  // namespace
 
-long long nb_mvee_work_doubles_impl(int n_problems, long long n_max, int d,
-                                    int n_batch) {
+// ---- the exports (include/nautilus_hip.h) and what they share --------------
+extern "C" int64_t nb_mvee_work_doubles(int32_t n_problems, int64_t n_max,
+                                        int32_t d, int32_t n_batch) {
   return (long long)n_problems * mv_prob_doubles(n_max, d, nsc_of(n_batch)) + 64;
 }
 
-long long nb_moments_work_doubles_impl(long long n, int d) {
+extern "C" int64_t nb_moments_work_doubles(int64_t n, int32_t d) {
   const int dt = (d + 1 + 15) / 16;
   return mom_partial_doubles(n, dt) + 16;
 }
 
 // S = sum_i w_i q_i q_i^T (w = null: unit weights), scaled, into out[m*m]
-int nb_launch_moments(const double* x, const double* w, long long n, int d,
-                      double scale, double* out, double* work,
-                      hipStream_t stream) {
+extern "C" int nb_weighted_moments(const double* x, const double* w, int64_t n,
+                                   int32_t d, double scale, double* out,
+                                   double* work, void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (x == nullptr || out == nullptr || work == nullptr) {
+    nb_set_error("null argument");
+    return NB_ERR_ARG;
+  }
   if (d < 1 || d > 128 || n < 1 || n > 2147483647LL / (d + 1)) {
-    nb_set_error("device moments: bad shape (n=%lld, n_dim=%d)", n, d);
+    nb_set_error("device moments: bad shape (n=%lld, n_dim=%d)", (long long)n,
+                 d);
     return NB_ERR_ARG;
   }
   const int dt = (d + 1 + 15) / 16;
@@ -913,9 +923,9 @@ int nb_launch_moments(const double* x, const double* w, long long n, int d,
 }
 
 // The Khachiyan iteration for n_problems point sets (standardised points).
-int nb_launch_mvee_batch(int n_problems, const double* const* xs,
-                         const long long* n, int d, int n_max, int n_batch,
-                         double* const* u, double* work, hipStream_t stream) {
+static int mvee_batch(int n_problems, const double* const* xs,
+                      const long long* n, int d, int n_max, int n_batch,
+                      double* const* u, double* work, hipStream_t stream) {
   if (d < 1 || d > 128) {
     nb_set_error("device MVEE supports n_dim <= 128 (got %d)", d);
     return NB_ERR_UNSUPPORTED;
@@ -1000,17 +1010,23 @@ int nb_launch_mvee_batch(int n_problems, const double* const* xs,
 }
 
 // out[0] = max_i q_i^T P q_i, q = (x, 1), P (m x m) symmetric in p_dev
-int nb_launch_quadform_max(const double* x, long long n, int d,
-                           const double* p_dev, double* out, double* work,
-                           hipStream_t stream) {
+extern "C" int nb_quadform_max(const double* x, int64_t n, int32_t d,
+                               const double* p_dev, double* out, double* work,
+                               void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (x == nullptr || p_dev == nullptr || out == nullptr || work == nullptr) {
+    nb_set_error("null argument");
+    return NB_ERR_ARG;
+  }
   if (d < 1 || d > 128 || n < 1 || n > 2147483647LL / (d + 1)) {
-    nb_set_error("quadratic form: bad shape (n=%lld, n_dim=%d)", n, d);
+    nb_set_error("quadratic form: bad shape (n=%lld, n_dim=%d)", (long long)n,
+                 d);
     return NB_ERR_ARG;
   }
   const int m = d + 1, dt = (m + 15) / 16;
   MvPlan pl;
   if (!mv_plan(n, &pl)) {
-    nb_set_error("quadratic form: too many points (n=%lld)", n);
+    nb_set_error("quadratic form: too many points (n=%lld)", (long long)n);
     return NB_ERR_UNSUPPORTED;
   }
   MvBatch mb;
@@ -1032,27 +1048,21 @@ int nb_launch_quadform_max(const double* x, long long n, int d,
   return NB_OK;
 }
 
-long long nb_quadform_work_doubles_impl() {
+extern "C" int64_t nb_quadform_work_doubles(void) {
   return 2LL * MV_MAXW * 20 + (2LL * MV_MAXW * 21 + 1) / 2 + 8;
 }
 
-long long nb_whiten_work_doubles_impl(long long n, int d) {
+extern "C" int64_t nb_whiten_work_doubles(int64_t n, int32_t d) {
   const int dt = (d + 15) / 16;
   return ((n * d + 1) & ~1LL) + mom_partial_doubles(n, (d + 1 + 15) / 16) +
          nb_ell_block_size(dt) + 16;
 }
 
-int nb_launch_standardize(const double* x, long long n, int d, double* mean,
-                          double* scale, double* out, hipStream_t stream);
-int nb_launch_transform(const double* ell_block, int dt, int n_dim,
-                        const double* x, long long n, double* y,
-                        hipStream_t stream);
-
 // xw = W ((x - mean) / sd): zero mean, unit covariance.  mean[d], sd[d],
 // w[d*d] (lower triangular, row-major) describe the map.
-int nb_launch_whiten(const double* x, long long n, int d, double* xw,
-                     double* mean, double* sd, double* w, double* work,
-                     hipStream_t stream) {
+static int whiten(const double* x, long long n, int d, double* xw,
+                  double* mean, double* sd, double* w, double* work,
+                  hipStream_t stream) {
   if (d < 1 || d > 128 || n <= d || n > 2147483647LL / (d + 1)) {
     nb_set_error("whitening needs n_dim < n, n_dim <= 128 (n=%lld, n_dim=%d)",
                  n, d);
@@ -1084,3 +1094,64 @@ int nb_launch_whiten(const double* x, long long n, int d, double* xw,
   NB_HIP_CHECK(hipGetLastError());
   return nb_launch_transform(ell, dt, d, xs, n, xw, stream);
 }
+
+extern "C" {
+
+int nb_mvee_khachiyan(int32_t n_problems, const double* const* xs,
+                      const int64_t* n_points, int32_t n_dim, int32_t n_max,
+                      int32_t n_batch, double* const* u, double* work,
+                      void* stream) {
+  if (n_problems < 1 || xs == nullptr || n_points == nullptr || u == nullptr ||
+      work == nullptr) {
+    nb_set_error("null argument");
+    return NB_ERR_ARG;
+  }
+  std::vector<long long> n(n_points, n_points + n_problems);
+  return mvee_batch(n_problems, xs, n.data(), n_dim, n_max, n_batch, u, work,
+                    (hipStream_t)stream);
+}
+
+int nb_whiten(const double* x, int64_t n, int32_t n_dim, double* xw,
+              double* mean, double* sd, double* w, double* work,
+              void* stream) {
+  if (x == nullptr || xw == nullptr || mean == nullptr || sd == nullptr ||
+      w == nullptr || work == nullptr) {
+    nb_set_error("null argument");
+    return NB_ERR_ARG;
+  }
+  return whiten(x, n, n_dim, xw, mean, sd, w, work, (hipStream_t)stream);
+}
+
+int64_t nb_mvee_weights_work_doubles(int64_t n, int32_t n_dim,
+                                     int32_t n_batch) {
+  return 2 * 16 * NB_MAX_DT + (int64_t)n_dim * n_dim + n * n_dim + 4 +
+         nb_whiten_work_doubles(n, n_dim) +
+         nb_mvee_work_doubles(1, n, n_dim, n_batch);
+}
+
+int nb_mvee_weights(const double* x, int64_t n, int32_t n_dim, int32_t n_max,
+                    int32_t n_batch, double* u, double* work, void* stream) {
+  if (x == nullptr || u == nullptr || work == nullptr) {
+    nb_set_error("null argument");
+    return NB_ERR_ARG;
+  }
+  if (n_dim < 1 || n_dim > 16 * NB_MAX_DT) {
+    nb_set_error("device MVEE supports n_dim <= 128 (got %d)", n_dim);
+    return NB_ERR_UNSUPPORTED;
+  }
+  // whitened copy of the points (the iteration is affine invariant)
+  double* mean = work;
+  double* scale = work + 16 * NB_MAX_DT;
+  double* wmat = scale + 16 * NB_MAX_DT;
+  double* xw = wmat + (((int64_t)n_dim * n_dim + 1) & ~(int64_t)1);
+  double* wh = xw + ((n * n_dim + 1) & ~(int64_t)1);
+  double* rest = wh + nb_whiten_work_doubles(n, n_dim);
+  int rc = whiten(x, n, n_dim, xw, mean, scale, wmat, wh, (hipStream_t)stream);
+  if (rc != NB_OK) return rc;
+  const double* xw_c = xw;
+  long long nn = n;
+  return mvee_batch(1, &xw_c, &nn, n_dim, n_max, n_batch, &u, rest,
+                    (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -33,6 +33,7 @@
 // inf happens to be.
 #include "../../include/nautilus_hip.h"          // NB_NOISE_ROW, NB_NOISE_FULL
 #include "nb_common.h"
+#include "nb_launch.h"
 #include "nb_poisson_log.h"
 
 namespace {

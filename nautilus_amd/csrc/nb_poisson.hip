@@ -32,6 +32,7 @@
 // wins over -inf.  Both are flags, OR-ed over the row, and a flagged row's sum
 // is discarded: nothing relies on what inf - inf happens to be.
 #include "nb_common.h"
+#include "nb_launch.h"
 #include "nb_poisson_term.h"
 
 namespace {

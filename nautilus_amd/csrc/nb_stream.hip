@@ -27,6 +27,7 @@
 //    (profiles/r05/fifth_session/stream_odd_ab.txt);
 //  * r^2 is reduced over the 4 lanes of a point with two xor-shuffles.
 #include "nb_common.h"
+#include "nb_launch.h"
 #include "nb_quadform.h"
 
 namespace {
@@ -181,7 +182,7 @@ __device__ __forceinline__ void stream_consume(
   const bool even = (n_dim & 1) == 0;
   // No masking of the loaded values: a slot past n_dim holds an element of
   // the point's own row (the clamped address) and meets exact zeros in the
-  // tiles (nb_api.hip packs B_inv[h][k] = 0 for k >= n_dim), a lane past the
+  // tiles (nb_pack.h packs B_inv[h][k] = 0 for k >= n_dim), a lane past the
   // end of the array computes on the last row and stores nothing.  (The
   // selects were ~4 of the ~6 VALU instructions per loaded pair, on a kernel
   // whose matrix pipe and memory system are both ~64 % busy.)
@@ -314,7 +315,7 @@ int launch(const double* cvec, const double* tiles, int n_dim, const double* x,
 
 }  // namespace
 
-// cvec / tiles point into the stream block of the blob (nb_common.h hdr[18]):
+// cvec / tiles point into the stream block of the blob (nb_layout.h hdr[18]):
 // c zero padded to 16*DT, then DT(DT+1)/2 lower-triangular 16x16 tiles of
 // W0[k][h] = B_inv[h][k] with the K permutation described above.
 int nb_launch_ell_stream(const double* cvec, const double* tiles, int n_dim,

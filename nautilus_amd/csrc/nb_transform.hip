@@ -5,6 +5,8 @@
 // evaluation (nb_tile.h), so the network is trained on exactly the inputs it
 // later sees inside nb_eval_kernel.
 #include "nb_tile.h"
+#include "nb_launch.h"
+#include "../../include/nautilus_hip.h"
 
 namespace {
 
@@ -323,9 +325,21 @@ nb_prior_table_kernel(const double* __restrict__ u, long long n, int d, int ls,
 
 }  // namespace
 
-int nb_launch_prior(const double* u, long long n, int d,
-                    const unsigned char* kind, const double* loc,
-                    const double* scale, double* out, hipStream_t stream) {
+extern "C" int nb_prior_transform(const double* u, int64_t n, int32_t d,
+                                  const uint8_t* kind, const double* loc,
+                                  const double* scale, double* out,
+                                  void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (d < 1 || d > 16 * NB_MAX_DT || kind == nullptr || loc == nullptr ||
+      scale == nullptr || (n > 0 && (!u || !out))) {
+    nb_set_error("bad prior transform arguments");
+    return NB_ERR_ARG;
+  }
+  for (int j = 0; j < d; ++j)
+    if (kind[j] > 1) {
+      nb_set_error("prior kind %d of parameter %d is not supported", kind[j], j);
+      return NB_ERR_UNSUPPORTED;
+    }
   if (n <= 0) return NB_OK;
   PriorArgs a;
   for (int j = 0; j < 16 * NB_MAX_DT; ++j) {
@@ -333,7 +347,7 @@ int nb_launch_prior(const double* u, long long n, int d,
     a.p0[j] = j < d ? loc[j] : 0.0;
     a.p1[j] = j < d ? scale[j] : 1.0;
   }
-  const long long total = n * d;
+  const long long total = (long long)n * d;
   long long blocks = (total + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(nb_prior_kernel, dim3((unsigned)blocks), dim3(256), 0,
@@ -421,4 +435,15 @@ int nb_launch_standardize(const double* x, long long n, int d, double* mean,
   }
   NB_HIP_CHECK(hipGetLastError());
   return NB_OK;
+}
+
+extern "C" int nb_standardize(const double* x, int64_t n, int32_t n_dim,
+                              double* mean, double* scale, double* out,
+                              void* stream) {
+  if (x == nullptr || mean == nullptr || scale == nullptr) {
+    nb_set_error("null argument");
+    return NB_ERR_ARG;
+  }
+  return nb_launch_standardize(x, n, n_dim, mean, scale, out,
+                               (hipStream_t)stream);
 }
