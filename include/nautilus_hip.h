@@ -398,12 +398,19 @@ int nb_prior_transform(const double* u_dev, int64_t n, int32_t n_dim,
                        const uint8_t* kind, const double* loc,
                        const double* scale, double* out_dev, void* stream);
 
-/* The same transform for six families, table-driven, with fixed and tied
- * parameters (prior.py:85-120 and the dictionary of prior.py:122-162).
+/* The same transform for seventeen families, table-driven, with fixed and
+ * tied parameters (prior.py:85-120 and the dictionary of prior.py:122-162).
  * kind: 0 uniform, 1 norm, 2 loguniform / reciprocal (shapes a, b),
- * 3 lognorm (shape s), 4 halfnorm, 5 truncnorm (shapes a, b); loc / scale /
- * shape0 / shape1 are host arrays of length n_dim (scipy's arguments; unused
- * shapes are ignored).  The prior has n_keys keys in order: key_column[k] is
+ * 3 lognorm (shape s), 4 halfnorm, 5 truncnorm (shapes a, b), and the
+ * families whose quantile function is a closed form: 7 cauchy, 8 halfcauchy,
+ * 9 laplace, 10 logistic, 11 gumbel_r, 12 gumbel_l, 13 weibull_min (shape
+ * c > 0), 14 rayleigh, 15 pareto (shape b > 0), 16 powerlaw (shape a > 0),
+ * 17 triang (shape 0 <= c <= 1); a shape out of range, not finite or (13,
+ * 15, 16) with an infinite reciprocal is NB_ERR_ARG.  Kind 6 is internal
+ * (below) and, like every kind above 17, NB_ERR_UNSUPPORTED from the caller.
+ * loc / scale / shape0 / shape1 are host arrays of length n_dim (scipy's
+ * arguments; the single shape of a family goes in shape0, unused shapes are
+ * ignored).  The prior has n_keys keys in order: key_column[k] is
  * the column of the free parameter that key k is (or is tied to), or -1 for
  * a fixed parameter with the constant key_value[k].  The table is uploaded
  * once, here; nb_prior_table_transform only launches, on the caller's stream

@@ -524,7 +524,8 @@ struct nb_prior_table {
   double* dev = nullptr;
   int n_dim = 0, n_keys = 0;
   int level = 0;            // kernel variant: 0 kinds 0 and 2 only, 1 with the
-                            // normal families, 2 with log-space truncnorm
+                            // normal families, 2 with log-space truncnorm;
+                            // 3 more with a closed-form kind (7 to 17)
   const double* par() const { return dev; }
   const double* key_value() const { return dev + NB_PRIOR_NPAR * (size_t)n_dim; }
   const int* key_column() const { return (const int*)(key_value() + n_keys); }

@@ -413,10 +413,28 @@ void pt_truncnorm_log_constants(double a, double b, double* out3) {
   out3[2] = (double)r1;
 }
 
+// The one shape of a closed-form kind (13 weibull_min, 15 pareto, 16
+// powerlaw: positive, finite, with a finite reciprocal -- the kernel
+// multiplies by it; 17 triang: in [0, 1]); false and the error text otherwise
+bool pt_check_shape(int kind, int j, double a) {
+  if (kind == 17) {
+    if (a >= 0.0 && a <= 1.0) return true;
+    nb_set_error("parameter %d: triangular needs a shape 0 <= c <= 1", j);
+    return false;
+  }
+  if (a > 0.0 && std::isfinite(a) && std::isfinite(1.0 / a)) return true;
+  nb_set_error("parameter %d: %s needs a finite shape %s > 0 with a finite "
+               "reciprocal", j,
+               kind == 13 ? "Weibull" : kind == 15 ? "Pareto" : "power law",
+               kind == 13 ? "c" : kind == 15 ? "b" : "a");
+  return false;
+}
+
 // The byte image of a prior table (nb_layout.h) and the kernel variant it
 // needs: 0 kinds 0 and 2 only, 1 with the normal families, 2 with log-space
-// truncnorm.  `out` is the handle pointer of the caller, tested for NULL with
-// the other arguments (so in every table packer below).
+// truncnorm; 3 more with a closed-form kind (7 to 17).  `out` is the handle
+// pointer of the caller, tested for NULL with the other arguments (so in
+// every table packer below).
 int pack_prior_table(int32_t n_dim, const uint8_t* kind, const double* loc,
                      const double* scale, const double* shape0,
                      const double* shape1, int32_t n_keys,
@@ -435,7 +453,7 @@ int pack_prior_table(int32_t n_dim, const uint8_t* kind, const double* loc,
   std::vector<unsigned char> kind_dev(kind, kind + d);
   for (int j = 0; j < n_dim; ++j) {
     const double a = shape0[j], b = shape1[j];
-    if (kind[j] > 5) {
+    if (kind[j] == 6 || kind[j] > 17) {
       nb_set_error("prior kind %d of parameter %d is not supported", kind[j], j);
       return NB_ERR_UNSUPPORTED;
     }
@@ -486,6 +504,13 @@ int pack_prior_table(int32_t n_dim, const uint8_t* kind, const double* loc,
         pt_truncnorm_constants(a, b, c3);
       }
       for (int t = 0; t < 3; ++t) par[(4 + t) * d + j] = c3[t];
+    } else if (kind[j] == 13 || kind[j] == 15 || kind[j] == 16) {
+      if (!pt_check_shape(kind[j], j, a)) return NB_ERR_ARG;
+      par[2 * d + j] = 1.0 / a;             // rounded once, as scipy forms it
+    } else if (kind[j] == 17) {
+      if (!pt_check_shape(kind[j], j, a)) return NB_ERR_ARG;
+      par[2 * d + j] = a;
+      par[3 * d + j] = 1.0 - a;
     }
   }
   for (int k = 0; k < n_keys; ++k)
@@ -504,11 +529,16 @@ int pack_prior_table(int32_t n_dim, const uint8_t* kind, const double* loc,
   std::memcpy(at, key_column, (size_t)n_keys * sizeof(int));
   at += (size_t)n_keys * sizeof(int);
   std::memcpy(at, kind_dev.data(), d);
-  *level = 0;
+  int base = 0, closed = 0;
   for (int j = 0; j < n_dim; ++j) {
+    if (kind[j] >= 7) {
+      closed = 3;
+      continue;
+    }
     const int need = kind_dev[j] == 6 ? 2 : (kind[j] != 0 && kind[j] != 2);
-    if (need > *level) *level = need;
+    if (need > base) base = need;
   }
+  *level = base + closed;
   return NB_OK;
 }
 

@@ -126,9 +126,10 @@ nb_prior_kernel(const double* __restrict__ u, long long total, int d,
 }
 
 
-// Table-driven prior transform: the same x_j = dist_j.isf(1 - u_j) for six
-// families, with the per-column table in device memory (uploaded once per
-// prior by nb_prior_table_create, nb_api.hip) instead of a by-value argument.
+// Table-driven prior transform: the same x_j = dist_j.isf(1 - u_j) for
+// seventeen families, with the per-column table in device memory (uploaded
+// once per prior by nb_prior_table_create, nb_api.hip) instead of a by-value
+// argument.
 //   kind  scipy name             z(q), then x = z * scale + loc
 //   0     uniform                1 - q
 //   1     norm                   -ndtri(q)
@@ -136,6 +137,7 @@ nb_prior_kernel(const double* __restrict__ u, long long total, int d,
 //   3     lognorm                exp(-s ndtri(q))
 //   4     halfnorm               -ndtri(q / 2)
 //   5     truncnorm              see pt_value (and pt_truncnorm_log)
+//   7-17  the closed-form tier   see pt_closed_form
 // Products and sums are rounded one by one (no contraction), as numpy does,
 // so that kind 0 equals scipy bit for bit whatever loc and scale are.
 //
@@ -195,24 +197,118 @@ __device__ __forceinline__ double pt_truncnorm_log(double qq, double a,
   return fmin(fmax(x, a), b);
 }
 
-// pt_value has ONE call site of normcdfinv and one of exp (the kinds differ
-// in the argument and in what is done with the result).  The library's
-// inverse normal distribution function alone takes more than 400 vector
-// registers, which leaves one wavefront per SIMD.  So the kernel comes in
-// three levels, chosen per table: 0 for kinds 0 and 2 only (44 registers:
-// flat and log-uniform priors stream at full occupancy), 1 with the normal
-// families, 2 with the log-space truncnorm as well (its erfcx / log loop costs
-// the others a few per cent when it is compiled in).
+// The closed-form tier (kinds 7 to 17): quantile functions that are a few
+// log / exp / sqrt / sinpi operations, z = dist.isf(q).
+//   kind  scipy name (shape)   z(q)                       rows PT_P0..
+//   7     cauchy               cot(pi q)
+//   8     halfcauchy           cot(pi q / 2)
+//   9     laplace              -log(2 q), q < 1/2; log(2 p) otherwise
+//   10    logistic             log(p / q)
+//   11    gumbel_r             -log(-log p)
+//   12    gumbel_l             log(-log q)
+//   13    weibull_min (c)      (-log q)^(1 / c)           1 / c
+//   14    rayleigh             sqrt(-2 log q)
+//   15    pareto (b)           q^(-1 / b)                 1 / b
+//   16    powerlaw (a)         p^(1 / a)                  1 / a
+//   17    triang (c)           sqrt(c p), p < c;          c, 1 - c
+//                              1 - sqrt((1 - c) q) otherwise
+// q is the given number and p = 1 - q is exact for q >= 1/2, so m, whichever
+// of the two is at most 1/2, is always exact, and the symmetric families
+// (7, 9, 10) are evaluated in the tail that m measures, with the sign of the
+// side: cot(pi q) = -cot(pi p), log(p / q) = log1p((1 - 2 m) / m) on the left
+// of the median and minus that on the right, where 1 - 2 m loses nothing.  The
+// argument of sincospi never leaves [0, 1/2], so no general-argument tan with
+// its reduction of large arguments is needed, and sinpi(0) = +0 gives the
+// infinite end its sign.
+// log p is formed as log1p(-q) where it matters (kind 11: -log p is the
+// ARGUMENT of a logarithm; kind 16 multiplies it by 1 / a and is content with
+// log of the rounded p).  Powers are exp(log(.) / shape) with the reciprocal
+// shape rounded once on the host, as scipy forms it.  The kind is the
+// wavefront's, so each case is a scalar branch and runs alone; inside a case
+// the two sides of the median share every library call.  The clamps of kinds
+// 15 and 16 cost one instruction and keep a likelihood that takes a logarithm
+// of x - loc - scale or of loc + scale - x safe whatever exp rounds to.
+__device__ __forceinline__ double pt_closed_form(int kind, double q, double p,
+                                                 const double* __restrict__ par,
+                                                 int d) {
+#pragma clang fp contract(off)
+  const bool low = q < 0.5;
+  const double m = low ? q : p;
+  double z, t;
+  switch (kind) {
+    case 7:
+    case 8: {
+      double s, c;
+      sincospi(kind == 7 ? m : 0.5 * q, &s, &c);
+      z = c / s;
+      if (kind == 7 && !low) z = -z;
+      break;
+    }
+    case 9:
+      t = log(2.0 * m);
+      z = low ? -t : t;
+      break;
+    case 10:
+      t = 2.0 * m;
+      t = 1.0 - t;
+      t = log1p(t / m);
+      z = low ? t : -t;
+      break;
+    case 11:
+      z = -log(fabs(log1p(-q)));
+      break;
+    case 12:
+      z = log(fabs(log(q)));
+      break;
+    case 13:
+      t = log(fabs(log(q)));
+      z = exp(t * par[PT_P0 * d]);
+      break;
+    case 14:
+      t = 2.0 * fabs(log(q));
+      z = sqrt(t);
+      break;
+    case 15:
+      t = fabs(log(q)) * par[PT_P0 * d];
+      z = fmax(exp(t), 1.0);
+      break;
+    case 16:
+      t = log(p) * par[PT_P0 * d];
+      z = fmin(exp(t), 1.0);
+      break;
+    default: {                                        // 17
+      const double c = par[PT_P0 * d];
+      const bool left = p < c;
+      t = left ? c * p : par[PT_P1 * d] * q;
+      t = sqrt(t);
+      z = left ? t : 1.0 - t;
+      break;
+    }
+  }
+  return z;
+}
+
+// pt_value has ONE call site of normcdfinv and one of exp for the kinds below
+// 7 (they differ in the argument and in what is done with the result).  The
+// library's inverse normal distribution function alone takes more than 400
+// vector registers, which leaves one wavefront per SIMD.  So the kernel comes
+// in three base levels, chosen per table: 0 for kinds 0 and 2 only (44
+// registers: flat and log-uniform priors stream at full occupancy), 1 with
+// the normal families, 2 with the log-space truncnorm as well (its erfcx /
+// log loop costs the others a few per cent when it is compiled in).  A table
+// with a closed-form kind runs level base + 3, the same code with
+// pt_closed_form compiled in; a table without one runs what it always ran.
 template <int LEVEL>
 __device__ __forceinline__ double pt_value(int kind, double u,
                                            const double* __restrict__ par,
                                            int d) {
 #pragma clang fp contract(off)
+  constexpr int BASE = LEVEL % 3;
   const double q = 1.0 - u;
   const double p = 1.0 - q;
   double z = p;                                       // kind 0
   bool upper = false;
-  if (LEVEL >= 1 && (kind == 1 || (kind >= 3 && kind <= 5))) {
+  if (BASE >= 1 && (kind == 1 || (kind >= 3 && kind <= 5))) {
     double arg = q;                                   // kinds 1, 3
     if (kind == 4) arg = q * 0.5;
     if (kind == 5) {
@@ -239,12 +335,13 @@ __device__ __forceinline__ double pt_value(int kind, double u,
     }
     z = exp(t);
   }
-  if (LEVEL >= 2 && kind == 6) {
+  if (BASE >= 2 && kind == 6) {
     const double sign = par[PT_P5 * d];
     z = sign * pt_truncnorm_log(sign < 0.0 ? p : q, par[PT_P0 * d],
                                 par[PT_P1 * d], par[PT_P2 * d], par[PT_P3 * d],
                                 par[PT_P4 * d]);
   }
+  if (LEVEL >= 3 && kind >= 7) z = pt_closed_form(kind, q, p, par, d);
   const double zs = z * par[PT_SCALE * d];
   return zs + par[PT_LOC * d];
 }
@@ -367,16 +464,19 @@ int nb_launch_prior_table(const double* u, long long n, int d,
   typedef void (*kernel_t)(const double*, long long, int, int, const double*,
                            const unsigned char*, int, const int*,
                            const double*, double*);
-  static const kernel_t kernels[6] = {
+  static const kernel_t kernels[12] = {
       nb_prior_table_kernel<false, 0>, nb_prior_table_kernel<false, 1>,
-      nb_prior_table_kernel<false, 2>, nb_prior_table_kernel<true, 0>,
-      nb_prior_table_kernel<true, 1>, nb_prior_table_kernel<true, 2>};
-  if (level < 0 || level > 2) {
+      nb_prior_table_kernel<false, 2>, nb_prior_table_kernel<false, 3>,
+      nb_prior_table_kernel<false, 4>, nb_prior_table_kernel<false, 5>,
+      nb_prior_table_kernel<true, 0>,  nb_prior_table_kernel<true, 1>,
+      nb_prior_table_kernel<true, 2>,  nb_prior_table_kernel<true, 3>,
+      nb_prior_table_kernel<true, 4>,  nb_prior_table_kernel<true, 5>};
+  if (level < 0 || level > 5) {
     nb_set_error("bad prior table level %d", level);
     return NB_ERR_ARG;
   }
-  const int which = 3 * (column_major != 0) + level;
-  static size_t allowed[6] = {0, 0, 0, 0, 0, 0};
+  const int which = 6 * (column_major != 0) + level;
+  static size_t allowed[12] = {};
   if (lds > allowed[which]) {
     const hipError_t e = hipFuncSetAttribute(
         (const void*)kernels[which],

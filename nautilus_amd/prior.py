@@ -4,7 +4,11 @@ with an ``isf`` method), fixed (a number) or tied to an earlier parameter (its
 name).  Numpy points are transformed on the host; cuda tensors (the batches of
 a device likelihood) are transformed on the GPU when every free parameter is
 a frozen scipy distribution of one of the families in ``DEVICE_KINDS``
-(``nb_prior_table_transform``)."""
+(``nb_prior_table_transform``): the uniform,
+normal and log families, and the families whose quantile function is a closed
+form -- ``cauchy``, ``halfcauchy``, ``laplace``, ``logistic``, ``gumbel_r``,
+``gumbel_l``, ``weibull_min``, ``rayleigh``, ``pareto``, ``powerlaw`` and
+``triang``."""
 
 import collections
 import numbers
@@ -17,9 +21,19 @@ FREE, FIXED, TIED = 'free', 'fixed', 'tied'
 # scipy name -> (kind of the device table, number of shape parameters)
 DEVICE_KINDS = {'uniform': (0, 0), 'norm': (1, 0), 'loguniform': (2, 2),
                 'reciprocal': (2, 2), 'lognorm': (3, 1), 'halfnorm': (4, 0),
-                'truncnorm': (5, 2)}
+                'truncnorm': (5, 2),
+                # kind 6 is the device's own (a truncnorm in log space)
+                'cauchy': (7, 0), 'halfcauchy': (8, 0), 'laplace': (9, 0),
+                'logistic': (10, 0), 'gumbel_r': (11, 0), 'gumbel_l': (12, 0),
+                'weibull_min': (13, 1), 'rayleigh': (14, 0),
+                'pareto': (15, 1), 'powerlaw': (16, 1), 'triang': (17, 1)}
 DEVICE_FAMILIES = ('uniform, norm, loguniform (reciprocal), lognorm, '
-                   'halfnorm, truncnorm')
+                   'halfnorm, truncnorm, cauchy, halfcauchy, laplace, '
+                   'logistic, gumbel_r, gumbel_l, weibull_min, rayleigh, '
+                   'pareto, powerlaw, triang')
+# kind -> (scipy's name of the family, of its shape), shape > 0 required
+POSITIVE_SHAPE = {13: ('weibull_min', 'c'), 15: ('pareto', 'b'),
+                  16: ('powerlaw', 'a')}
 # NB_PRIOR_TRUNCNORM_MAX: the device refuses a truncnorm further out
 TRUNCNORM_MAX = 1e150
 
@@ -56,6 +70,11 @@ def _device_row(dist):
     if kind == 5 and (s0 > TRUNCNORM_MAX or s1 < -TRUNCNORM_MAX):
         return 'its interval lies more than %g standard deviations from ' \
             'the mean' % TRUNCNORM_MAX
+    if kind in POSITIVE_SHAPE and not (0 < s0 < np.inf and
+                                       np.isfinite(1.0 / s0)):
+        return '%s needs a finite %s > 0' % POSITIVE_SHAPE[kind]
+    if kind == 17 and not 0 <= s0 <= 1:
+        return 'triang needs 0 <= c <= 1'
     return (kind, loc, scale, s0, s1)
 
 
@@ -195,7 +214,13 @@ class Prior:
 
         ``expon`` is deliberately not a device kind, simple as its transform
         is: ``tests/test_host_logic.py::test_prior_device_spec`` uses it as
-        the example of a distribution that keeps a prior on the host."""
+        the example of a distribution that keeps a prior on the host.
+        ``weibull_min(1, loc=..., scale=...)`` is the device spelling of an
+        exponential prior.  The closed-form families (kinds 7 to 17) take no
+        shape, except ``weibull_min`` (c > 0), ``pareto`` (b > 0),
+        ``powerlaw`` (a > 0) and ``triang`` (0 <= c <= 1), whose one shape is
+        ``shape0``; a shape outside its range keeps the prior on the host,
+        as scipy itself would only return nan for it."""
         return self._cached()['table']
 
     @property
