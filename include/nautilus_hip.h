@@ -621,6 +621,67 @@ int nb_noise_loglike(const nb_noise* h, int32_t mode, const double* model_dev,
                      int64_t n, double* out_dev, void* stream);
 int nb_noise_destroy(nb_noise* h);
 
+/* Gaussian-process likelihood of P measurements d (the user-side callable of
+ * sampler.py:863-873 for a model prediction m(theta) under correlated noise
+ * whose covariance depends on the point), one launch with one workgroup per
+ * point that builds K_i in LDS, factorises it and never stores it:
+ *   out_dev[i] = log_norm - 1/2 [ r_i^T K_i^-1 r_i + log det K_i ],
+ *   r_i = m_i - d,
+ *   mode NB_GP_HYPER:  K_i[j,k] = a_i rho(dist[j,k] / l_i) +
+ *                      delta_jk (sigma2_j + s_i), row i of the covariance input
+ *                      holding the three doubles (a_i, l_i, s_i): signal
+ *                      variance, length scale, jitter variance; rho is the
+ *                      handle's kernel, with r = dist / l,
+ *                        NB_GP_SQEXP     exp(-r^2 / 2)
+ *                        NB_GP_EXP       exp(-r)
+ *                        NB_GP_MATERN32  (1 + sqrt(3) r) exp(-sqrt(3) r)
+ *                        NB_GP_MATERN52  (1 + sqrt(5) r + 5 r^2 / 3)
+ *                                        exp(-sqrt(5) r)
+ *                      and the diagonal a_i + sigma2_j + s_i exactly;
+ *   mode NB_GP_FULL:   K_i = C_i + diag(sigma2), row i of the covariance input
+ *                      holding the P * P row-major doubles of C_i, of which the
+ *                      lower triangle (k <= j) alone is read.
+ * With log_norm = -(P/2) log 2 pi the result is log N(d | m_i, K_i).
+ * nb_gp_create: data [P] finite; sigma2 [P] = sigma^2, finite and >= 0, or
+ * NULL (= 0); dist [P * P] row-major, symmetric, finite, >= 0 with a zero
+ * diagonal, or NULL for a handle that is never used in hyper mode: host
+ * arrays, read here and uploaded once.  NB_ERR_ARG: n_data outside
+ * 1..NB_GP_MAX_DATA, an unknown kernel, NULL or non-finite data, a negative or
+ * non-finite sigma2, a dist that is not as described, a non-finite log_norm.
+ * nb_gp_loglike (sampler.py:863-873) only launches, on the caller's stream
+ * (one handle serves any number of streams): row i of the model is the n_data
+ * doubles at model_dev + i * ld, row i of the covariance input the 3 or
+ * n_data * n_data doubles at cov_dev + i * ld_cov (NB_ERR_ARG for an unknown
+ * mode, for NB_GP_HYPER on a handle created without dist, for ld < n_data or
+ * ld_cov < 3 resp. n_data * n_data with n > 1, and for a NULL pointer with
+ * n > 0).
+ * A row is NaN, and changes no other row, with an m_ij that is not finite; an
+ * a that is negative or not finite (a = 0 is legal: white noise only); an l
+ * outside (0, +inf); an s that is negative or not finite; a non-finite entry
+ * of the lower triangle of C; or a pivot of the factorisation that is not in
+ * (0, +inf), i.e. a K that is not positive definite to working precision
+ * (sigma2_j = 0 is legal as long as the diagonal stays positive).  The bits
+ * of a row depend on P, the kernel, the mode and the row's own inputs only:
+ * not on n, its position in the batch, ld, ld_cov, the stream or the grid.
+ * n = 0 returns NB_OK without a launch.
+ *  nb_gp_destroy frees the handle of the same callable (sampler.py:863-873);
+ * NULL is NB_OK.                                                            */
+typedef struct nb_gp nb_gp;
+#define NB_GP_MAX_DATA 128
+#define NB_GP_SQEXP 0
+#define NB_GP_EXP 1
+#define NB_GP_MATERN32 2
+#define NB_GP_MATERN52 3
+#define NB_GP_HYPER 0
+#define NB_GP_FULL 1
+int nb_gp_create(int32_t n_data, const double* data, const double* sigma2,
+                 const double* dist, int32_t kernel, double log_norm,
+                 nb_gp** out);
+int nb_gp_loglike(const nb_gp* h, int32_t mode, const double* model_dev,
+                  int64_t ld, const double* cov_dev, int64_t ld_cov,
+                  int64_t n, double* out_dev, void* stream);
+int nb_gp_destroy(nb_gp* h);
+
 
 /* Two-stage evaluation of bounds with several outer members, several neural
  * bounds, or of lists of bounds (bounds/union.py:285-289, 316-319;

@@ -20,6 +20,7 @@ _LAZY = {
     'GaussianDataLikelihood': 'likelihoods',
     'PoissonDataLikelihood': 'likelihoods',
     'GaussianNoiseLikelihood': 'likelihoods',
+    'GaussianProcessLikelihood': 'likelihoods',
     'RosenbrockLikelihood': 'likelihoods', 'FunnelLikelihood': 'likelihoods',
 }
 

@@ -747,6 +747,57 @@ int nb_noise_loglike(const nb_noise* h, int32_t mode, const double* model,
                          n, h->log_norm, out, as_stream(stream));
 }
 
+// Data, sigma^2 and the distance tiles for nb_gp.hip (nb_layout.h,
+// nb_gp_tile), uploaded once.
+struct nb_gp {
+  double* dev = nullptr;
+  int n_data = 0;
+  int kernel = 0;
+  bool has_dist = false;
+  double log_norm = 0.0;
+};
+
+int nb_gp_create(int32_t n_data, const double* data, const double* sigma2,
+                 const double* dist, int32_t kernel, double log_norm,
+                 nb_gp** out) {
+  std::vector<double> image;
+  const int rc = pack_gp(n_data, data, sigma2, dist, kernel, log_norm, out,
+                         &image);
+  nb_gp h;
+  h.n_data = n_data;
+  h.kernel = kernel;
+  h.has_dist = dist != nullptr;
+  h.log_norm = log_norm;
+  return nb_make_table(rc, image, "Gaussian-process likelihood", h, out);
+}
+
+int nb_gp_destroy(nb_gp* h) { return nb_destroy_table(h); }
+
+int nb_gp_loglike(const nb_gp* h, int32_t mode, const double* model,
+                  int64_t ld, const double* cov, int64_t ld_cov, int64_t n,
+                  double* out, void* stream) {
+  if (h == nullptr || n < 0 || (mode != NB_GP_HYPER && mode != NB_GP_FULL)) {
+    nb_set_error("bad Gaussian-process likelihood arguments (a handle, "
+                 "n >= 0, mode NB_GP_HYPER or NB_GP_FULL)");
+    return NB_ERR_ARG;
+  }
+  if (mode == NB_GP_HYPER && !h->has_dist) {
+    nb_set_error("bad Gaussian-process likelihood arguments (NB_GP_HYPER "
+                 "needs a handle created with dist)");
+    return NB_ERR_ARG;
+  }
+  const int64_t width =
+      mode == NB_GP_HYPER ? 3 : (int64_t)h->n_data * h->n_data;
+  if ((n > 1 && (ld < h->n_data || ld_cov < width)) ||
+      (n > 0 && (model == nullptr || cov == nullptr || out == nullptr))) {
+    nb_set_error("bad Gaussian-process likelihood arguments (ld >= n_data, "
+                 "ld_cov >= %lld, no NULL pointer)", (long long)width);
+    return NB_ERR_ARG;
+  }
+  return nb_launch_gp(h->dev, h->n_data, h->kernel, mode, model, ld, cov,
+                      ld_cov, n, h->log_norm, out, as_stream(stream));
+}
+
 int nb_ellipsoid_contains_stream(const nb_bound* b, const double* x, int64_t n,
                                  uint8_t* mask, void* stream) {
   if (!b->at.single_full) {

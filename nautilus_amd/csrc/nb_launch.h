@@ -65,6 +65,10 @@ int nb_launch_noise(const double* tab, int n_data, int mode,
                     const double* model, long long ld, const double* noise,
                     long long ld_noise, long long n, double log_norm,
                     double* out, hipStream_t stream);
+int nb_launch_gp(const double* tab, int n_data, int kernel, int mode,
+                 const double* model, long long ld, const double* cov,
+                 long long ld_cov, long long n, double log_norm, double* out,
+                 hipStream_t stream);
 int nb_launch_fold_poisson(const double* blob, int n_data, int n_src,
                            const double* src, long long ld, long long n,
                            double log_const, double* out, hipStream_t stream);

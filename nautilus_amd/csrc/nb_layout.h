@@ -145,6 +145,29 @@ constexpr size_t nb_fold_r_offset(int dt) {
   return 64 * (size_t)dt;
 }
 
+// Gaussian-process likelihood (nb_gp.hip), T = ceil(P / 16).  The table is d
+// and sigma^2, each zero padded to 16 T doubles, then -- unless the handle was
+// made without distances -- the distance matrix as the T (T + 1) / 2 tiles of
+// its lower triangle: tile (ti, tj), tj <= ti, is number nb_gp_tile(ti, tj)
+// and holds element (row 16 ti + r, column 16 tj + c) at nb_gp_index(r, c),
+// column-major, so that k-step s of an fp64 MFMA operand is the 64 contiguous
+// doubles from 64 s on.  Rows and columns from P on hold zeros, and so does
+// the part of a diagonal tile above the diagonal.  The kernel keeps K in LDS
+// in the same order (nb_gp_lds_doubles: the tiles, the residual, the pivots,
+// the y of a panel, 16 reciprocals and a flag word).
+constexpr int nb_gp_tile(int ti, int tj) { return ti * (ti + 1) / 2 + tj; }
+constexpr int nb_gp_index(int r, int c) { return 16 * c + r; }
+constexpr int nb_gp_tiles(int t) { return t * (t + 1) / 2; }
+constexpr int nb_gp_dist_offset(int t) { return 32 * t; }
+constexpr int nb_gp_table_doubles(int t, bool with_dist) {
+  return nb_gp_dist_offset(t) + (with_dist ? nb_gp_tiles(t) * NB_TILE : 0);
+}
+constexpr int nb_gp_lds_doubles(int t) {
+  return nb_gp_tiles(t) * NB_TILE + 2 * 16 * t + 16 + 16 + 2;
+}
+// wavefronts of a workgroup at T tiles
+constexpr int nb_gp_waves(int t) { return t <= 2 ? 1 : t <= 4 ? 2 : 4; }
+
 // Prior table (nb_transform.hip, PT_* rows): one allocation holding
 // par[NB_PRIOR_NPAR][n_dim], key_value[n_keys], key_column[n_keys] (int) and
 // kind[n_dim] (bytes), in that order (doubles first, so everything is aligned).

@@ -800,4 +800,52 @@ int pack_noise(int32_t n_data, const double* data, const double* sigma2,
   return NB_OK;
 }
 
+// Data, sigma^2 and the distance tiles for nb_gp.hip (nb_layout.h,
+// nb_gp_tile / nb_gp_index); dist may be absent
+int pack_gp(int32_t n_data, const double* data, const double* sigma2,
+            const double* dist, int32_t kernel, double log_norm,
+            const void* out, std::vector<double>* image) {
+  if (out == nullptr || data == nullptr || n_data < 1 ||
+      n_data > NB_GP_MAX_DATA || kernel < NB_GP_SQEXP ||
+      kernel > NB_GP_MATERN52 || !std::isfinite(log_norm)) {
+    nb_set_error("bad Gaussian-process likelihood arguments (n_data 1..%d, "
+                 "data, a kernel NB_GP_SQEXP .. NB_GP_MATERN52, a finite "
+                 "log_norm)", NB_GP_MAX_DATA);
+    return NB_ERR_ARG;
+  }
+  const size_t p = (size_t)n_data;
+  const int t = (n_data + 15) / 16;
+  std::vector<double>& host = *image;
+  host.assign((size_t)nb_gp_table_doubles(t, dist != nullptr), 0.0);
+  for (size_t j = 0; j < p; ++j) {
+    if (!std::isfinite(data[j])) {
+      nb_set_error("data point %zu must be finite", j);
+      return NB_ERR_ARG;
+    }
+    host[j] = data[j];
+    if (sigma2 == nullptr) continue;
+    if (!std::isfinite(sigma2[j]) || sigma2[j] < 0.0) {
+      nb_set_error("sigma2 %zu must be finite and not negative", j);
+      return NB_ERR_ARG;
+    }
+    host[16 * (size_t)t + j] = sigma2[j];
+  }
+  if (dist == nullptr) return NB_OK;
+  double* tiles = host.data() + nb_gp_dist_offset(t);
+  for (size_t j = 0; j < p; ++j)
+    for (size_t k = 0; k <= j; ++k) {
+      const double v = dist[j * p + k];
+      if (!std::isfinite(v) || v < 0.0 || v != dist[k * p + j] ||
+          (j == k && v != 0.0)) {
+        nb_set_error("dist entry (%zu, %zu) must be finite, not negative, "
+                     "equal to entry (%zu, %zu) and zero on the diagonal",
+                     j, k, k, j);
+        return NB_ERR_ARG;
+      }
+      tiles[(size_t)nb_gp_tile((int)(j / 16), (int)(k / 16)) * NB_TILE +
+            nb_gp_index((int)(j % 16), (int)(k % 16))] = v;
+    }
+  return NB_OK;
+}
+
 }  // namespace

@@ -788,6 +788,66 @@ class NoiseTable(_Table):
             (noise, noise.shape[1], ld_noise), head=(mode,))
 
 
+GP_HYPER, GP_FULL = 0, 1           # NB_GP_HYPER, NB_GP_FULL
+GP_KERNELS = {'sqexp': 0, 'exp': 1, 'matern32': 2, 'matern52': 3}  # NB_GP_*
+GP_MAX_DATA = 128                  # NB_GP_MAX_DATA
+
+
+def gp_launch_shape(n_data):
+    """(T, W) of ``nb_gp_loglike`` at P = ``n_data`` (nb_gp.hip,
+    ``launch_mode``; nb_layout.h, ``nb_gp_waves``): the kernel is instantiated
+    for T = ceil(P / 16) tiles of 16 rows and a workgroup has W wavefronts."""
+    if not 1 <= n_data <= GP_MAX_DATA:
+        raise ValueError('n_data must be 1..%d, not %d' %
+                         (GP_MAX_DATA, n_data))
+    t = (n_data + 15) // 16
+    return t, 1 if t <= 2 else 2 if t <= 4 else 4
+
+
+class GPTable(_Table):
+    """Device-resident measurements of a Gaussian-process likelihood
+    (``nb_gp_create``): ``data`` (P,) finite, ``sigma2`` (P,) = sigma^2 >= 0
+    (None = 0), ``dist`` (P, P) the symmetric matrix of distances with a zero
+    diagonal (None for a handle used in GP_FULL mode only) and ``kernel`` a
+    key of ``GP_KERNELS``, with ``log_norm`` added to every result.  Packed
+    and uploaded once; every ``loglike`` is one launch on the current
+    stream."""
+
+    _destroy = 'nb_gp_destroy'
+
+    def __init__(self, data, sigma2=None, dist=None, kernel='sqexp',
+                 log_norm=0.0):
+        data = _data_vector(data, 'data')
+        self.n_data = p = len(data)
+        sigma2 = _shape_p(sigma2, p, 'sigma2')
+        if dist is not None:
+            dist = _f64(dist)
+            if dist.shape != (p, p):
+                raise ValueError('dist must have shape (%d, %d)' % (p, p))
+        if kernel not in GP_KERNELS:
+            raise ValueError('kernel must be one of %s, not %r' %
+                             (sorted(GP_KERNELS), kernel))
+        self._create('nb_gp_create', p, _dp(data), _dp(sigma2), _dp(dist),
+                     GP_KERNELS[kernel], float(log_norm))
+
+    def loglike(self, model, cov, mode, ld=None, ld_cov=None):
+        """log L of the rows of the cuda float64 tensors ``model`` (n, P) and
+        ``cov`` ((n, 3) with ``mode`` GP_HYPER; (n, P, P) or (n, P * P) with
+        GP_FULL, every matrix contiguous), both read in place
+        (``_rows_loglike``)."""
+        n = model.shape[0]
+        if cov.shape[0] != n:
+            raise ValueError('model and cov must have the same number of '
+                             'rows, not %d and %d' % (n, cov.shape[0]))
+        width = 3 if mode == GP_HYPER else self.n_data * self.n_data
+        return self._rows_loglike(
+            self._lib.nb_gp_loglike, (model, self.n_data, ld),
+            (cov, width, ld_cov), head=(mode,))
+
+
+GP = GPTable
+
+
 def gmm_fit(x, n_init=10, seed=0, tol=1e-3, reg_covar=1e-6, max_iter=100,
             init_labels=None):
     """Two-component full-covariance Gaussian mixture fits (one per restart)

@@ -717,6 +717,240 @@ class GaussianNoiseLikelihood(_ModelLikelihood):
         return out
 
 
+N_GP_MAX = 128                     # NB_GP_MAX_DATA of nautilus_hip.h
+GP_KERNELS = ('sqexp', 'exp', 'matern32', 'matern52')
+
+
+def gp_correlation(kernel, r):
+    """The isotropic correlation function rho(r) of ``kernel`` at r = D / l
+    >= 0, with the operations and their order of ``gp_rho`` in nb_gp.hip;
+    numpy float64 or ``np.longdouble`` in, the same type out."""
+    r = np.asarray(r)
+    ty = r.dtype.type
+    r = np.minimum(r, ty(1e4))         # rho is 0 in float64 long before
+    if kernel == 'sqexp':
+        return np.exp(-ty(0.5) * (r * r))
+    if kernel == 'exp':
+        return np.exp(-r)
+    if kernel == 'matern32':
+        u = np.sqrt(ty(3)) * r
+        return (1 + u) * np.exp(-u)
+    if kernel == 'matern52':
+        u = np.sqrt(ty(5)) * r
+        return ((1 + u) + (u * u) * (1 / ty(3))) * np.exp(-u)
+    raise ValueError('kernel must be one of %s, not %r' %
+                     (', '.join(map(repr, GP_KERNELS)), kernel))
+
+
+class GaussianProcessLikelihood(_ModelLikelihood):
+    """Gaussian-process likelihood of P correlated measurements whose full
+    covariance depends on the point:
+
+        log L(theta) = log_norm - 1/2 [ r^T K^-1 r + log det K ],
+        r = m(theta) - data.
+
+    ``log_norm = -(P/2) log 2 pi``, or 0 with ``normalised=False``; the
+    determinant depends on the point and always stays.
+
+    ``t`` holds the P input locations, (P,) or (P, d), of which the Euclidean
+    distances D_jk = |t_j - t_k| alone are kept; ``data`` the P finite
+    measurements, P at most 128; ``sigma`` the P fixed error bars, finite and
+    >= 0 (``None`` = all zero).  ``model`` takes the (n, n_dim) batch of
+    points as a torch tensor and returns a pair of float64 tensors on the
+    same device: ``m`` the (n, P) mean prediction and
+
+      cov='hyper'  ``h`` (n, 3) with columns (a, l, s) -- signal variance,
+                   length scale and a jitter variance added in quadrature:
+                   K_jk = a rho(D_jk / l) + delta_jk (sigma_j^2 + s), where
+                   rho is ``kernel``, a function of r = D / l:
+                     'sqexp'     exp(-r^2 / 2)
+                     'exp'       exp(-r)
+                     'matern32'  (1 + sqrt(3) r) exp(-sqrt(3) r)
+                     'matern52'  (1 + sqrt(5) r + 5 r^2 / 3) exp(-sqrt(5) r)
+                   and the diagonal is a + sigma_j^2 + s exactly;
+      cov='full'   ``C`` (n, P, P):  K = C + diag(sigma^2), any covariance
+                   model; only the lower triangle (k <= j) of every C is
+                   read, ``t`` may be ``None`` and ``kernel`` is ignored.
+
+    A call evaluates the model and then runs the fused kernel
+    ``nb_gp_loglike`` -- one launch on the current stream with one workgroup
+    per point, which builds K in on-chip memory, factorises it on the fp64
+    matrix cores and never stores it, so that the (n, P, P) tensor of hyper
+    mode never exists.  ``from_model`` is the second half alone; it reads a
+    cuda tensor whose rows are strided (``stride(1) == 1``, ``stride(0)`` at
+    least the width, such as a column slice of a wider tensor; for ``C`` every
+    matrix contiguous and the matrices any distance >= P^2 apart) in place
+    and copies anything else to contiguous, separately for the two outputs.
+    ``numpy`` / ``numpy_from_model`` are the pure-numpy twins (LAPACK's
+    Cholesky, one matrix at a time), ``numpy_covariance`` the K they
+    factorise.
+
+    Row i is NaN when any m_ij is not finite; when a is negative or not
+    finite (a = 0 is legal: white noise only), l is outside (0, +inf) or s is
+    negative or not finite; when the lower triangle of C holds a non-finite
+    entry; or when K is not positive definite to working precision (a pivot
+    of the factorisation outside (0, +inf)).  That changes no bit of any
+    other row."""
+
+    _pair = True
+    _what = 'the model output and the covariance input'
+
+    def __init__(self, model, t, data, sigma=None, *, kernel='sqexp',
+                 cov='hyper', normalised=True):
+        super().__init__(model)
+        if cov not in ('hyper', 'full'):
+            raise ValueError("cov must be 'hyper' or 'full', not %r" % (cov,))
+        self.cov = cov
+        if kernel not in GP_KERNELS:
+            raise ValueError('kernel must be one of %s, not %r' %
+                             (', '.join(map(repr, GP_KERNELS)), kernel))
+        self.kernel = kernel
+        data = _bounded_vector(data, 'data', N_GP_MAX, 'data points')
+        if not np.all(np.isfinite(data)):
+            raise ValueError('data must be finite')
+        self.data = data.copy()
+        self.n_data = p = len(data)
+        if t is None:
+            if cov == 'hyper':
+                raise ValueError("cov='hyper' needs the input locations t")
+            self.t = self.dist = None
+        else:
+            t = np.asarray(t, float)
+            if t.ndim not in (1, 2) or t.shape[0] != p or \
+                    (t.ndim == 2 and t.shape[1] < 1):
+                raise ValueError('t must have shape (%d,) or (%d, d), not %s'
+                                 % (p, p, t.shape))
+            if not np.all(np.isfinite(t)):
+                raise ValueError('t must be finite')
+            self.t = t.copy()
+            tt = t.reshape(p, -1)
+            with np.errstate(over='ignore'):
+                self.dist = np.sqrt(np.sum(
+                    (tt[:, None, :] - tt[None, :, :])**2, axis=2))
+            if not np.all(np.isfinite(self.dist)):
+                raise ValueError('t is too spread out: a distance is not '
+                                 'finite')
+        if sigma is None:
+            self.sigma = np.zeros(p)
+        else:
+            self.sigma = _numbers(sigma, p, 'sigma', False).copy()
+        with np.errstate(over='ignore'):
+            self._sigma2 = self.sigma * self.sigma
+        if not np.all(np.isfinite(self._sigma2)):
+            raise ValueError('sigma is too large: sigma^2 is not finite')
+        self.log_norm = -0.5 * p * np.log(2 * np.pi) if normalised else 0.0
+
+    @property
+    def _width(self):
+        return 3 if self.cov == 'hyper' else self.n_data * self.n_data
+
+    def _make_table(self):
+        return device.GPTable(self.data, self._sigma2, self.dist,
+                              kernel=self.kernel, log_norm=self.log_norm)
+
+    def _widths(self):
+        return self.n_data, self._width
+
+    def _loglike(self, m, c):
+        return self._table().loglike(
+            m, c, device.GP_HYPER if self.cov == 'hyper' else device.GP_FULL)
+
+    def _check(self, m, c):
+        super()._check(m)
+        if c.ndim != 2 or tuple(c.shape) != (m.shape[0], self._width):
+            raise ValueError('the covariance input must have shape %s, not %s'
+                             % (self._cov_shape(m.shape[0]), tuple(c.shape)))
+
+    def _cov_shape(self, n):
+        if self.cov == 'hyper':
+            return (n, 3)
+        return (n, self.n_data, self.n_data)
+
+    def _flat(self, c):
+        """The (n, P, P) covariances as (n, P^2) rows: a view where every
+        matrix is contiguous, a copy otherwise."""
+        p = self.n_data
+        if self.cov == 'hyper' or c.ndim != 3 or \
+                tuple(c.shape[1:]) != (p, p):
+            return c
+        n = c.shape[0]
+        if not isinstance(c, torch.Tensor):
+            return np.ascontiguousarray(c).reshape(n, p * p)
+        if n > 0 and (p == 1 or (c.stride(2) == 1 and c.stride(1) == p)):
+            return c.as_strided((n, p * p), (c.stride(0), 1))
+        return c.contiguous().view(n, p * p)
+
+    def from_model(self, m, c):
+        """log L of the rows of an (n, P) float64 model output and its
+        covariance input ((n, 3) or (n, P, P)): cuda tensors in, a cuda
+        tensor out; numpy in, numpy out."""
+        if isinstance(m, torch.Tensor) != isinstance(c, torch.Tensor):
+            raise ValueError('the model output and the covariance input must '
+                             'both be torch tensors or both numpy arrays')
+        if not isinstance(c, torch.Tensor):
+            c = np.asarray(c)
+        if self.cov == 'full' and (c.ndim != 3 or tuple(c.shape[1:]) !=
+                                   (self.n_data, self.n_data)):
+            raise ValueError('the covariance input must have shape %s, not %s'
+                             % (self._cov_shape(len(m)), tuple(c.shape)))
+        return self._from_outputs(m, self._flat(c))
+
+    def numpy_covariance(self, m, c):
+        """The (n, P, P) covariances K of an (n, P) model output and its
+        covariance input in pure numpy, as they come (symmetric, built from
+        the lower triangle; nothing is marked here)."""
+        m, c = np.asarray(m, float), np.asarray(c, float)
+        self._check(m, self._flat(c))
+        n, p = m.shape
+        diag = np.arange(p)
+        with np.errstate(all='ignore'):
+            if self.cov == 'hyper':
+                a, l, s = (c[:, i, None, None] for i in range(3))
+                k = a * gp_correlation(self.kernel, self.dist * (1.0 / l))
+                k[:, diag, diag] = a[:, 0] + (self._sigma2 + s[:, 0])
+                return k
+            low = np.tril(c.reshape(n, p, p))
+            k = low + np.transpose(np.tril(low, -1), (0, 2, 1))
+            k[:, diag, diag] += self._sigma2
+            return k
+
+    def numpy_from_model(self, m, c):
+        """Pure-numpy evaluation of an (n, P) model output and its covariance
+        input (CPU baseline / oracle runs / tests)."""
+        from scipy.linalg import solve_triangular
+        m, c = np.asarray(m, float), np.asarray(c, float)
+        k = self.numpy_covariance(m, c)
+        n, p = m.shape
+        low = np.tril(np.ones((p, p), bool))
+        good = np.all(np.isfinite(m), axis=1) & \
+            np.all(np.isfinite(k[:, low]), axis=1)
+        if self.cov == 'hyper':
+            a, l, s = c.T
+            with np.errstate(invalid='ignore'):
+                good &= (a >= 0) & (a < np.inf) & (l > 0) & (l < np.inf) & \
+                    (s >= 0) & (s < np.inf)
+        out = np.full(n, np.nan)
+        rows = np.flatnonzero(good)
+        try:
+            chol = dict(zip(rows, np.linalg.cholesky(k[rows])))
+        except np.linalg.LinAlgError:
+            chol = {}
+            for i in rows:
+                try:
+                    chol[i] = np.linalg.cholesky(k[i])
+                except np.linalg.LinAlgError:
+                    pass
+        for i, low_i in chol.items():
+            d = np.diag(low_i)
+            if not np.all((d > 0) & (d < np.inf)):
+                continue
+            y = solve_triangular(low_i, m[i] - self.data, lower=True,
+                                 check_finite=False)
+            out[i] = self.log_norm - 0.5 * (np.sum(y * y) +
+                                            2.0 * np.sum(np.log(d)))
+        return out
+
+
 class RosenbrockLikelihood:
     """Rosenbrock function on x = low + (high - low) u (BASELINE config 3):
     log L = -sum_i [a (x_{i+1} - x_i^2)^2 + (1 - x_i)^2] --
