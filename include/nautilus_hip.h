@@ -682,6 +682,65 @@ int nb_gp_loglike(const nb_gp* h, int32_t mode, const double* model_dev,
                   int64_t n, double* out_dev, void* stream);
 int nb_gp_destroy(nb_gp* h);
 
+/* The same Gaussian-process likelihood for a long ORDERED series (the
+ * user-side callable of sampler.py:863-873 for a model prediction m(theta) of
+ * a time series under correlated noise), as an O(P) filter: one launch, one
+ * lane per point, one sequential pass over the series that builds no matrix:
+ *   out_dev[i] = log_norm - 1/2 [ r_i^T K_i^-1 r_i + log det K_i ],
+ *   r_i = m_i - d,
+ *   K_i[j,k] = a_i rho(|t_j - t_k| / l_i) + delta_jk (sigma2_j + s_i),
+ * row i of the hyper input holding (a_i, l_i, s_i) -- signal variance, length
+ * scale, jitter variance -- and for NB_GPS_SHO a fourth double q_i, the
+ * quality factor.  rho is the handle's kernel, with r = |t_j - t_k| / l,
+ *   NB_GPS_EXP       exp(-r)
+ *   NB_GPS_MATERN32  (1 + sqrt(3) r) exp(-sqrt(3) r)
+ *   NB_GPS_MATERN52  (1 + sqrt(5) r + 5 r^2 / 3) exp(-sqrt(5) r)
+ *   NB_GPS_SHO       exp(-r / (2 q)) [cos(eta r) + sin(eta r) / (2 eta q)],
+ *                    eta = sqrt(1 - 1 / (4 q^2)): the underdamped oscillator
+ *                    of frequency 1 / l
+ * the covariances of linear stochastic differential equations with 1, 2, 3
+ * and 2 states; the recursion is written out in nb_gps.hip.  For the first
+ * three K is that of nb_gp_loglike with the same kernel.  A gap t_j - t_j-1
+ * enters as min((t_j - t_j-1) / l, 1e4), beyond which the exponentials of the
+ * first three kernels are 0 in float64 (for NB_GPS_SHO that holds up to q of
+ * about 7; a larger q with a gap beyond 1e4 l sees the gap shortened).
+ * With log_norm = -(P/2) log 2 pi the result is log N(d | m_i, K_i).
+ * nb_gps_create: t [P] finite and non-decreasing (equal neighbours are
+ * legal), with finite differences; data [P] finite; sigma2 [P] = sigma^2,
+ * finite and >= 0, or NULL (= 0): host arrays, read here and uploaded once
+ * (the differences t_j - t_j-1, rounded once, are what the kernel reads).
+ * NB_ERR_ARG: n_data outside 1..NB_GPS_MAX_DATA, an unknown kernel, a NULL t
+ * or data, a t, data or sigma2 that is not as described, a non-finite
+ * log_norm.
+ * nb_gps_loglike (sampler.py:863-873) only launches, on the caller's stream
+ * (one handle serves any number of streams): row i of the model is the n_data
+ * doubles at model_dev + i * ld, row i of the hyper input the 3 (NB_GPS_SHO:
+ * 4) doubles at hyper_dev + i * ld_hyper (NB_ERR_ARG for ld < n_data or
+ * ld_hyper < 3 resp. 4 with n > 1, and for a NULL pointer with n > 0).
+ * A row is NaN, and changes no other row, with an m_ij that is not finite; an
+ * a that is negative or not finite (a = 0 is legal: white noise only); an l
+ * outside (0, +inf); an s that is negative or not finite; a q outside (1/2,
+ * +inf); or a pivot d_j of the recursion that is not in (0, +inf) (sigma2_j =
+ * 0 is legal as long as the pivots stay positive).  The bits of a row depend
+ * on P, the kernel and the row's own inputs only: not on n, its position in
+ * the batch, ld, ld_hyper, the stream or the grid.  n = 0 returns NB_OK
+ * without a launch.
+ *  nb_gps_destroy frees the handle of the same callable (sampler.py:863-873);
+ * NULL is NB_OK.                                                            */
+typedef struct nb_gps nb_gps;
+#define NB_GPS_MAX_DATA (1 << 20)
+#define NB_GPS_EXP 0
+#define NB_GPS_MATERN32 1
+#define NB_GPS_MATERN52 2
+#define NB_GPS_SHO 3
+int nb_gps_create(int32_t n_data, const double* t, const double* data,
+                  const double* sigma2, int32_t kernel, double log_norm,
+                  nb_gps** out);
+int nb_gps_loglike(const nb_gps* h, const double* model_dev, int64_t ld,
+                   const double* hyper_dev, int64_t ld_hyper, int64_t n,
+                   double* out_dev, void* stream);
+int nb_gps_destroy(nb_gps* h);
+
 
 /* Two-stage evaluation of bounds with several outer members, several neural
  * bounds, or of lists of bounds (bounds/union.py:285-289, 316-319;

@@ -21,6 +21,7 @@ _LAZY = {
     'PoissonDataLikelihood': 'likelihoods',
     'GaussianNoiseLikelihood': 'likelihoods',
     'GaussianProcessLikelihood': 'likelihoods',
+    'GaussianProcessSeriesLikelihood': 'likelihoods',
     'RosenbrockLikelihood': 'likelihoods', 'FunnelLikelihood': 'likelihoods',
 }
 

@@ -798,6 +798,51 @@ int nb_gp_loglike(const nb_gp* h, int32_t mode, const double* model,
                       ld_cov, n, h->log_norm, out, as_stream(stream));
 }
 
+// Steps, data and sigma^2 for nb_gps.hip (nb_layout.h, NB_GPS_STRIDE),
+// uploaded once.
+struct nb_gps {
+  double* dev = nullptr;
+  int n_data = 0;
+  int kernel = 0;
+  double log_norm = 0.0;
+};
+
+int nb_gps_create(int32_t n_data, const double* t, const double* data,
+                  const double* sigma2, int32_t kernel, double log_norm,
+                  nb_gps** out) {
+  std::vector<double> image;
+  const int rc = pack_gps(n_data, t, data, sigma2, kernel, log_norm, out,
+                          &image);
+  nb_gps h;
+  h.n_data = n_data;
+  h.kernel = kernel;
+  h.log_norm = log_norm;
+  return nb_make_table(rc, image, "Gaussian-process series likelihood", h,
+                       out);
+}
+
+int nb_gps_destroy(nb_gps* h) { return nb_destroy_table(h); }
+
+int nb_gps_loglike(const nb_gps* h, const double* model, int64_t ld,
+                   const double* hyper, int64_t ld_hyper, int64_t n,
+                   double* out, void* stream) {
+  if (h == nullptr || n < 0) {
+    nb_set_error("bad Gaussian-process series likelihood arguments (a "
+                 "handle, n >= 0)");
+    return NB_ERR_ARG;
+  }
+  const int64_t width = h->kernel == NB_GPS_SHO ? 4 : 3;
+  if ((n > 1 && (ld < h->n_data || ld_hyper < width)) ||
+      (n > 0 && (model == nullptr || hyper == nullptr || out == nullptr))) {
+    nb_set_error("bad Gaussian-process series likelihood arguments (ld >= "
+                 "n_data, ld_hyper >= %lld, no NULL pointer)",
+                 (long long)width);
+    return NB_ERR_ARG;
+  }
+  return nb_launch_gps(h->dev, h->n_data, h->kernel, model, ld, hyper,
+                       ld_hyper, n, h->log_norm, out, as_stream(stream));
+}
+
 int nb_ellipsoid_contains_stream(const nb_bound* b, const double* x, int64_t n,
                                  uint8_t* mask, void* stream) {
   if (!b->at.single_full) {

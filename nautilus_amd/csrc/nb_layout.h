@@ -168,6 +168,20 @@ constexpr int nb_gp_lds_doubles(int t) {
 // wavefronts of a workgroup at T tiles
 constexpr int nb_gp_waves(int t) { return t <= 2 ? 1 : t <= 4 ? 2 : 4; }
 
+// Gaussian-process likelihood of an ordered series (nb_gps.hip).  The table is
+// NB_GPS_STRIDE doubles per datum j: dt_j = t_j - t_j-1 rounded once (dt_0 =
+// 0), d_j, sigma_j^2 and a zero -- 32 aligned bytes, one scalar load of the
+// wavefront per step.  The kernel stages the model's rows through LDS in
+// blocks of NB_GPS_BLOCK columns.
+#define NB_GPS_STRIDE 4
+#define NB_GPS_DT 0
+#define NB_GPS_DATA 1
+#define NB_GPS_SIGMA2 2
+#define NB_GPS_BLOCK 32
+constexpr size_t nb_gps_table_doubles(int p) {
+  return (size_t)NB_GPS_STRIDE * (size_t)p;
+}
+
 // Prior table (nb_transform.hip, PT_* rows): one allocation holding
 // par[NB_PRIOR_NPAR][n_dim], key_value[n_keys], key_column[n_keys] (int) and
 // kind[n_dim] (bytes), in that order (doubles first, so everything is aligned).

@@ -848,4 +848,54 @@ int pack_gp(int32_t n_data, const double* data, const double* sigma2,
   return NB_OK;
 }
 
+// The steps t_j - t_j-1, data and sigma^2 for nb_gps.hip (nb_layout.h,
+// NB_GPS_STRIDE doubles per datum)
+int pack_gps(int32_t n_data, const double* t, const double* data,
+             const double* sigma2, int32_t kernel, double log_norm,
+             const void* out, std::vector<double>* image) {
+  if (out == nullptr || t == nullptr || data == nullptr || n_data < 1 ||
+      n_data > NB_GPS_MAX_DATA || kernel < NB_GPS_EXP ||
+      kernel > NB_GPS_SHO || !std::isfinite(log_norm)) {
+    nb_set_error("bad Gaussian-process series likelihood arguments (n_data "
+                 "1..%d, t, data, a kernel NB_GPS_EXP .. NB_GPS_SHO, a finite "
+                 "log_norm)", NB_GPS_MAX_DATA);
+    return NB_ERR_ARG;
+  }
+  const size_t p = (size_t)n_data;
+  std::vector<double>& host = *image;
+  host.assign(nb_gps_table_doubles(n_data), 0.0);
+  for (size_t j = 0; j < p; ++j) {
+    double* e = host.data() + NB_GPS_STRIDE * j;
+    if (!std::isfinite(t[j])) {
+      nb_set_error("t %zu must be finite", j);
+      return NB_ERR_ARG;
+    }
+    if (j > 0) {
+      if (t[j] < t[j - 1]) {
+        nb_set_error("t must not decrease: t %zu is below t %zu", j, j - 1);
+        return NB_ERR_ARG;
+      }
+      const double dt = t[j] - t[j - 1];
+      if (!std::isfinite(dt)) {
+        nb_set_error("t %zu is too far from t %zu: the step is not finite",
+                     j, j - 1);
+        return NB_ERR_ARG;
+      }
+      e[NB_GPS_DT] = dt;
+    }
+    if (!std::isfinite(data[j])) {
+      nb_set_error("data point %zu must be finite", j);
+      return NB_ERR_ARG;
+    }
+    e[NB_GPS_DATA] = data[j];
+    if (sigma2 == nullptr) continue;
+    if (!std::isfinite(sigma2[j]) || sigma2[j] < 0.0) {
+      nb_set_error("sigma2 %zu must be finite and not negative", j);
+      return NB_ERR_ARG;
+    }
+    e[NB_GPS_SIGMA2] = sigma2[j];
+  }
+  return NB_OK;
+}
+
 }  // namespace

@@ -848,6 +848,50 @@ class GPTable(_Table):
 GP = GPTable
 
 
+GPS_KERNELS = {'exp': 0, 'matern32': 1, 'matern52': 2, 'sho': 3}  # NB_GPS_*
+GPS_MAX_DATA = 1 << 20             # NB_GPS_MAX_DATA
+GPS_BLOCK = 32                     # NB_GPS_BLOCK of nb_layout.h: the columns
+#                                    of a block nb_gps.hip stages through LDS
+
+
+class GPSTable(_Table):
+    """Device-resident ordered series of a Gaussian-process likelihood
+    evaluated as a filter (``nb_gps_create``): ``t`` (P,) finite and
+    non-decreasing, ``data`` (P,) finite, ``sigma2`` (P,) = sigma^2 >= 0
+    (None = 0) and ``kernel`` a key of ``GPS_KERNELS``, with ``log_norm``
+    added to every result.  Packed and uploaded once; every ``loglike`` is
+    one launch on the current stream."""
+
+    _destroy = 'nb_gps_destroy'
+
+    def __init__(self, t, data, sigma2=None, kernel='matern32', log_norm=0.0):
+        data = _data_vector(data, 'data')
+        self.n_data = p = len(data)
+        t = _shape_p(t, p, 't')
+        sigma2 = _shape_p(sigma2, p, 'sigma2')
+        if kernel not in GPS_KERNELS:
+            raise ValueError('kernel must be one of %s, not %r' %
+                             (sorted(GPS_KERNELS), kernel))
+        self.width = 4 if kernel == 'sho' else 3
+        self._create('nb_gps_create', p, _dp(t), _dp(data), _dp(sigma2),
+                     GPS_KERNELS[kernel], float(log_norm))
+
+    def loglike(self, model, hyper, ld=None, ld_hyper=None):
+        """log L of the rows of the cuda float64 tensors ``model`` (n, P) and
+        ``hyper`` ((n, 3) with columns (a, l, s); (n, 4) with a column q for
+        'sho'), both read in place (``_rows_loglike``)."""
+        n = model.shape[0]
+        if hyper.shape[0] != n:
+            raise ValueError('model and hyper must have the same number of '
+                             'rows, not %d and %d' % (n, hyper.shape[0]))
+        return self._rows_loglike(
+            self._lib.nb_gps_loglike, (model, self.n_data, ld),
+            (hyper, self.width, ld_hyper))
+
+
+GPS = GPSTable
+
+
 def gmm_fit(x, n_init=10, seed=0, tol=1e-3, reg_covar=1e-6, max_iter=100,
             init_labels=None):
     """Two-component full-covariance Gaussian mixture fits (one per restart)

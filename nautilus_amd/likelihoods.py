@@ -951,6 +951,252 @@ class GaussianProcessLikelihood(_ModelLikelihood):
         return out
 
 
+N_GPS_MAX = 1 << 20                # NB_GPS_MAX_DATA of nautilus_hip.h
+GPS_KERNELS = ('exp', 'matern32', 'matern52', 'sho')
+GPS_CAP = 1e4                      # of dt / l, the cap of gp_correlation
+
+
+def sho_correlation(r, q):
+    """rho(r; q) = exp(-r / (2 q)) [cos(eta r) + sin(eta r) / (2 eta q)], eta
+    = sqrt(1 - 1 / (4 q^2)): the correlation of the underdamped oscillator of
+    quality factor q > 1/2 at r = |dt| / l >= 0, capped as ``gp_correlation``
+    caps r; numpy float64 or ``np.longdouble`` in, the same type out."""
+    r = np.asarray(r)
+    ty = r.dtype.type
+    r = np.minimum(r, ty(GPS_CAP))
+    w = 1 / (2 * np.asarray(q, r.dtype))
+    eta = np.sqrt(1 - w * w)
+    return np.exp(-(r * w)) * (np.cos(eta * r) + np.sin(eta * r) / eta * w)
+
+
+def sum_in_order(terms):
+    """The terms added from the first on, as the kernels add them."""
+    total = None
+    for term in terms:
+        total = term if total is None else total + term
+    return total
+
+
+class GaussianProcessSeriesLikelihood(_ModelLikelihood):
+    """Gaussian-process likelihood of an ordered series of P correlated
+    measurements, evaluated as a filter in O(P) per point:
+
+        log L(theta) = log_norm - 1/2 [ r^T K^-1 r + log det K ],
+        r = m(theta) - data,
+        K_jk = a rho(|t_j - t_k| / l) + delta_jk (sigma_j^2 + s).
+
+    This is the likelihood of ``GaussianProcessLikelihood(cov='hyper')`` for
+    a one-dimensional ``t`` and the kernels whose process is a linear
+    stochastic differential equation with a finite state -- which lifts the
+    limit on P from 128 to 2^20.  ``log_norm = -(P/2) log 2 pi``, or 0 with
+    ``normalised=False``.
+
+    ``t`` holds the P sampling times, finite and non-decreasing (equal
+    neighbours are legal; nothing is sorted here, because the model's columns
+    follow ``t``); ``data`` the P finite measurements; ``sigma`` the P fixed
+    error bars, finite and >= 0 (``None`` = all zero).  ``model`` takes the
+    (n, n_dim) batch of points as a torch tensor and returns a pair of
+    float64 tensors on the same device: ``m`` the (n, P) mean prediction and
+    ``h`` the (n, 3) hyper-parameters with columns (a, l, s) -- signal
+    variance, length scale and a jitter variance added in quadrature -- or,
+    for 'sho', (n, 4) with a fourth column q.  ``kernel`` is, as a function
+    of r = |dt| / l,
+
+      'exp'       exp(-r)                                       1 state
+      'matern32'  (1 + sqrt(3) r) exp(-sqrt(3) r)               2 states
+      'matern52'  (1 + sqrt(5) r + 5 r^2 / 3) exp(-sqrt(5) r)   3 states
+      'sho'       exp(-r / (2 q)) [cos(eta r) + sin(eta r) / (2 eta q)],
+                  eta = sqrt(1 - 1 / (4 q^2)), q > 1/2          2 states
+
+    the first three those of ``gp_correlation``, the last the underdamped
+    oscillator of frequency 1 / l and quality factor q (``sho_correlation``;
+    its critically damped limit q = 1/2 is 'matern32' with l / sqrt(3)).
+    The squared exponential has no finite state and is refused.
+
+    A call evaluates the model and then runs the fused kernel
+    ``nb_gps_loglike`` -- one launch on the current stream with one lane per
+    point, which walks the series once with a state of at most 3 x 3 numbers
+    and builds no matrix.  ``from_model`` is the second half alone; it reads
+    a cuda tensor whose rows are strided (``stride(1) == 1``, ``stride(0)`` at
+    least the width, such as a column slice of a wider tensor) in place and
+    copies anything else to contiguous, separately for ``m`` and ``h``.
+    ``numpy`` / ``numpy_from_model`` are the pure-numpy twins: the same
+    recursion with the same operations in the same order, vectorised over
+    the rows.
+
+    A gap enters as min(dt / l, 1e4), the cap of ``gp_correlation``: beyond
+    it the two sides are independent (for 'sho' that is so up to q of about
+    7; a larger q with a gap beyond 1e4 l sees the gap shortened).
+
+    Row i is NaN when any m_ij is not finite; when a is negative or not
+    finite (a = 0 is legal: white noise only), l is outside (0, +inf), s is
+    negative or not finite or, for 'sho', q is outside (1/2, +inf); or when a
+    pivot of the recursion -- the predictive variance of a measurement given
+    the earlier ones -- is outside (0, +inf).  That changes no bit of any
+    other row."""
+
+    _pair = True
+    _what = 'the model output and the hyper-parameters'
+
+    def __init__(self, model, t, data, sigma=None, *, kernel='matern32',
+                 normalised=True):
+        super().__init__(model)
+        if kernel == 'sqexp':
+            raise ValueError("kernel 'sqexp' has no finite state: no filter "
+                             'evaluates it; GaussianProcessLikelihood does, '
+                             'up to %d data points' % N_GP_MAX)
+        if kernel not in GPS_KERNELS:
+            raise ValueError('kernel must be one of %s, not %r' %
+                             (', '.join(map(repr, GPS_KERNELS)), kernel))
+        self.kernel = kernel
+        data = _bounded_vector(data, 'data', N_GPS_MAX, 'data points')
+        if not np.all(np.isfinite(data)):
+            raise ValueError('data must be finite')
+        self.data = data.copy()
+        self.n_data = p = len(data)
+        t = np.asarray(t, float)
+        if t.shape != (p,):
+            raise ValueError('t must have shape (%d,), not %s' % (p, t.shape))
+        if not np.all(np.isfinite(t)):
+            raise ValueError('t must be finite')
+        with np.errstate(over='ignore'):
+            dt = np.diff(t, prepend=t[0])
+        if np.any(dt < 0):
+            raise ValueError('t must not decrease (it is not sorted here: the '
+                             "model's columns follow t)")
+        if not np.all(np.isfinite(dt)):
+            raise ValueError('t is too spread out: a step is not finite')
+        self.t = t.copy()
+        self._dt = dt
+        if sigma is None:
+            self.sigma = np.zeros(p)
+        else:
+            self.sigma = _numbers(sigma, p, 'sigma', False).copy()
+        with np.errstate(over='ignore'):
+            self._sigma2 = self.sigma * self.sigma
+        if not np.all(np.isfinite(self._sigma2)):
+            raise ValueError('sigma is too large: sigma^2 is not finite')
+        self.log_norm = -0.5 * p * np.log(2 * np.pi) if normalised else 0.0
+
+    @property
+    def _width(self):
+        return 4 if self.kernel == 'sho' else 3
+
+    def _make_table(self):
+        return device.GPSTable(self.t, self.data, self._sigma2,
+                               kernel=self.kernel, log_norm=self.log_norm)
+
+    def _widths(self):
+        return self.n_data, self._width
+
+    def _check(self, m, h):
+        super()._check(m)
+        if h.ndim != 2 or tuple(h.shape) != (m.shape[0], self._width):
+            raise ValueError('the hyper-parameters must have shape (%d, %d), '
+                             'not %s' % (m.shape[0], self._width,
+                                         tuple(h.shape)))
+
+    def from_model(self, m, h):
+        """log L of the rows of an (n, P) float64 model output and its (n, 3)
+        or (n, 4) hyper-parameters: cuda tensors in, a cuda tensor out; numpy
+        in, numpy out."""
+        if isinstance(m, torch.Tensor) != isinstance(h, torch.Tensor):
+            raise ValueError('the model output and the hyper-parameters must '
+                             'both be torch tensors or both numpy arrays')
+        return self._from_outputs(m, h)
+
+    def _transition(self, r, w, eta, inv_eta):
+        """Phi at the capped r = dt / l of every row, as ``gps_phi`` of
+        nb_gps.hip builds it: a list of rows of (n,) arrays."""
+        ty = r.dtype.type
+        if self.kernel == 'exp':
+            return [[np.exp(-r)]]
+        if self.kernel == 'matern32':
+            x = np.sqrt(ty(3)) * r
+            e = np.exp(-x)
+            ex = e * x
+            return [[e * (1 + x), ex], [-ex, e * (1 - x)]]
+        if self.kernel == 'matern52':
+            x = np.sqrt(ty(5)) * r
+            e = np.exp(-x)
+            x2 = x * x
+            hx = ty(0.5) * x2
+            return [[e * ((1 + x) + hx), e * (x + x2), e * hx],
+                    [-(e * hx), e * ((1 + x) - x2), e * (x - hx)],
+                    [e * (hx - x), e * (x2 - 3 * x),
+                     e * ((1 - 2 * x) + hx)]]
+        e = np.exp(-(r * w))
+        arg = eta * r
+        c = np.cos(arg)
+        sg = np.sin(arg) * inv_eta
+        sw = sg * w
+        es = e * sg
+        return [[e * (c + sw), es], [-es, e * (c - sw)]]
+
+    def numpy_from_model(self, m, h, dtype=np.float64):
+        """Pure-numpy evaluation of an (n, P) model output and its
+        hyper-parameters (CPU baseline / oracle runs / tests): the recursion
+        of nb_gps.hip with its operations in its order, vectorised over the
+        rows, in ``dtype`` -- ``np.longdouble`` gives the tests their truth.
+        Every ``dtype`` starts from the same float64 inputs."""
+        m, h = np.asarray(m, float), np.asarray(h, float)
+        self._check(m, h)
+        ty = np.dtype(dtype).type
+        n, p = m.shape
+        a, l, s = (h[:, i].astype(ty) for i in range(3))
+        with np.errstate(all='ignore'):
+            bad = ~((a >= 0) & (a < np.inf)) | ~((l > 0) & (l < np.inf)) | \
+                ~((s >= 0) & (s < np.inf))
+            inv_l = np.minimum(1 / l, ty(np.finfo(np.float64).max))
+            w = eta = inv_eta = None
+            states = {'exp': 1, 'matern32': 2, 'matern52': 3, 'sho': 2}[
+                self.kernel]
+            if self.kernel == 'sho':
+                q = h[:, 3].astype(ty)
+                bad |= ~((q > 0.5) & (q < np.inf))
+                w = 1 / (2 * q)
+                eta = np.sqrt(1 - w * w)
+                inv_eta = 1 / eta
+            rr = range(states)
+            zero = np.zeros(n, ty)
+            big_g = [[zero for _ in rr] for _ in rr]
+            g = [zero for _ in rr]
+            q_sum, q_low, l_sum = zero, zero, zero
+            md = m.astype(ty)
+            for j in range(p):
+                r = np.minimum(ty(self._dt[j]) * inv_l, ty(GPS_CAP))
+                phi = self._transition(r, w, eta, inv_eta)
+                t = [[sum_in_order(phi[i][k] * big_g[k][c] for k in rr)
+                      for c in rr] for i in rr]
+                for i in rr:
+                    for c in range(i + 1):
+                        big_g[i][c] = big_g[c][i] = sum_in_order(
+                            t[i][k] * phi[c][k] for k in rr)
+                gn = [sum_in_order(phi[i][k] * g[k] for k in rr) for i in rr]
+                noise = ty(self._sigma2[j]) + s
+                d = (a - big_g[0][0]) + noise
+                v = (md[:, j] - ty(self.data[j])) - gn[0]
+                bad |= ~np.isfinite(md[:, j]) | ~((d > 0) & (d < np.inf))
+                inv_d = 1 / d
+                u = [a - big_g[0][0], -big_g[1][0] if states > 1 else None,
+                     a * -(1 / ty(3)) - big_g[2][0] if states > 2 else None]
+                k = [u[i] * inv_d for i in rr]
+                g = [gn[i] + k[i] * v for i in rr]
+                for i in rr:
+                    for c in range(i + 1):
+                        big_g[i][c] = big_g[c][i] = big_g[i][c] + u[i] * k[c]
+                # G00 + u0 k0 in the form that is a exactly without noise
+                big_g[0][0] = a - noise * k[0]
+                y = (v * v) * inv_d - q_low          # a compensated sum
+                q_new = q_sum + y
+                q_low = (q_new - q_sum) - y
+                q_sum = q_new
+                l_sum = l_sum + np.log(d)
+            out = ty(self.log_norm) - ty(0.5) * (q_sum + l_sum)
+        out = np.where(bad, ty(np.nan), out)
+        return out
+
+
 class RosenbrockLikelihood:
     """Rosenbrock function on x = low + (high - low) u (BASELINE config 3):
     log L = -sum_i [a (x_{i+1} - x_i^2)^2 + (1 - x_i)^2] --
