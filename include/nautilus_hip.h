@@ -111,19 +111,26 @@ int nb_boundlist_destroy(nb_boundlist* list);
 
 /* contains(points) of any bound: basic.py:51-67, 344-360, 594-617,
  * union.py:269-289, bounds/neural.py:99-126, nautilus.py:146-169.
- * mask_dev[i] = 1 if point i is inside.                                     */
+ * mask_dev[i] = 1 if point i is inside, else 0.
+ *
+ * nb_contains, nb_contains_any and nb_first_containing run the two stages of
+ * nb_list_eval (below) and nb_accept, for a bound its fused kernel does not
+ * take, those of nb_accept_staged -- in work space they allocate and free in
+ * stream order on `stream` (hipMallocAsync / hipFreeAsync), so calls on
+ * different streams may share a handle.  NB_ERR_HIP if the allocation fails;
+ * nb_list_eval / nb_accept_staged take work space the caller owns.          */
 int nb_contains(const nb_bound* bound, const double* x_dev, int64_t n,
                 uint8_t* mask_dev, void* stream);
 
 /* Shell exclusion (sampler.py:796-798): mask_dev[i] = 1 if ANY bound of the
- * list contains point i (bounds are tested in list order, a tile of points
- * stops as soon as all of its points are decided).                          */
+ * list contains point i, else 0 (all 0 for an empty list).                  */
 int nb_contains_any(const nb_boundlist* list, const double* x_dev, int64_t n,
                     uint8_t* mask_dev, void* stream);
 
 /* Shell association (sampler.py:1192-1221): idx_dev[i] = position in the list
- * of the FIRST bound that contains point i, -1 if none (pass the bounds from
- * the highest index down to get the reference's association).               */
+ * of the FIRST bound that contains point i, -1 if none or if the list is
+ * empty (pass the bounds from the highest index down to get the reference's
+ * association).                                                             */
 int nb_first_containing(const nb_boundlist* list, const double* x_dev,
                         int64_t n, int32_t* idx_dev, void* stream);
 
@@ -133,7 +140,8 @@ int nb_member_count(const nb_bound* bound, const double* x_dev, int64_t n,
 
 /* Ellipsoid-frame radius and emulator score of neural bound 0 of `bound`:
  * out_dev[2i] = |B_inv (x_i - c)|^2 (basic.py:340,360), out_dev[2i+1] =
- * NeuralNetworkEmulator.predict(transform(x_i)) (neural.py:100-116).        */
+ * NeuralNetworkEmulator.predict(transform(x_i)) (neural.py:100-116), 0 for a
+ * bound without networks.                                                   */
 int nb_neural_score(const nb_bound* bound, const double* x_dev, int64_t n,
                     double* out_dev, void* stream);
 
@@ -148,7 +156,9 @@ int nb_propose(const nb_bound* bound, uint64_t seed, uint64_t offset,
 /* Acceptance of the proposals written by nb_propose with the same (seed,
  * offset): flags_dev[i] bit0 = kept by the outer union (unit-cube clip,
  * union.py:313-314, and u > 1 - 1/k, union.py:316-319), bit1 = also inside
- * any NeuralBound (nautilus.py:217-219).                                    */
+ * any NeuralBound (nautilus.py:217-219).  One neural bound with networks and
+ * at most one outer member: one fused kernel; any other bound: the stages of
+ * nb_accept_staged in stream-ordered work space (see nb_contains).          */
 int nb_accept(const nb_bound* bound, uint64_t seed, uint64_t offset,
               const double* x_dev, int64_t n, uint8_t* flags_dev,
               void* stream);

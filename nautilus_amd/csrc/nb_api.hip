@@ -34,6 +34,7 @@ struct nb_bound {
   // two-stage queries: the bound's (neural bound) groups, {0} as group base
   FastGroup* groups_dev = nullptr;
   int* group_base_dev = nullptr;
+  int group_base[2] = {0, 0};               // host copy: {0, n_groups}
   int n_groups = 0;
 };
 
@@ -65,9 +66,25 @@ static void nb_append_groups(const nb_bound* b, int pos,
   }
 }
 
+// counters of the bound-evaluation kernels (nb_launch.h, nb_set_eval_counters)
+static unsigned long long* g_eval_counters = nullptr;
+void nb_eval_set_counters(unsigned long long* dev) { g_eval_counters = dev; }
+unsigned long long* nb_eval_counters() { return g_eval_counters; }
+
 namespace {
 
 inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
+
+// What a list query leaves (nautilus_hip.h, nb_list_eval: status 2 = inside,
+// first bound INT32_MAX = none) as nb_contains* / nb_first_containing return
+// it, in place: masks of 0 / 1, -1 for no bound
+__global__ void nb_query_out_kernel(unsigned char* mask, int* idx,
+                                    long long n) {
+  const long long i = blockIdx.x * 256ll + threadIdx.x;
+  if (i >= n) return;
+  if (mask != nullptr) mask[i] = (mask[i] & 2) != 0 ? 1 : 0;
+  if (idx != nullptr && idx[i] == INT32_MAX) idx[i] = -1;
+}
 
 // One device allocation of n elements (and `slack` zeroed ones after them)
 // filled from the host; freed again if that fails
@@ -129,9 +146,9 @@ int nb_bound_create(const nb_bound_desc* d, nb_bound** out) {
   if (rc != NB_OK) return rc;
   nb_bound* b = new nb_bound();
   b->at = at;
-  // (the kernels stage parts of the blob in whole 1 KB pieces -- dma_weights,
-  // the ellipsoid block of nb_eval_fast.hip -- so the last piece of the last
-  // block may read up to 1 KB past its end: keep that inside the allocation)
+  // (nb_eval_fast.hip stages parts of the blob in whole 1 KB pieces -- the
+  // weights, the ellipsoid block -- so the last piece of the last block may
+  // read up to 1 KB past its end: keep that inside the allocation)
   constexpr size_t SLACK = 512;
   hipError_t e = upload_array(&b->blob_dev, buf.data(), buf.size(), SLACK);
   if (e == hipSuccess) {
@@ -142,8 +159,8 @@ int nb_bound_create(const nb_bound_desc* d, nb_bound** out) {
     std::vector<FastGroup> groups;
     nb_append_groups(b, 0, groups);
     b->n_groups = (int)groups.size();
-    const int base[2] = {0, b->n_groups};
-    e = upload_array(&b->group_base_dev, base, 2);
+    b->group_base[1] = b->n_groups;
+    e = upload_array(&b->group_base_dev, b->group_base, 2);
     if (e == hipSuccess && b->n_groups > 0)
       e = upload_array(&b->groups_dev, groups.data(), groups.size());
   }
@@ -224,54 +241,6 @@ int nb_boundlist_destroy(nb_boundlist* l) {
   return NB_OK;
 }
 
-int nb_contains(const nb_bound* b, const double* x, int64_t n, uint8_t* mask,
-                void* stream) {
-  return nb_launch_eval(b->at.dt, b->self_list_dev, 1, 0, x, n, mask, nullptr,
-                        nullptr, 0, 0, as_stream(stream));
-}
-
-int nb_contains_any(const nb_boundlist* l, const double* x, int64_t n,
-                    uint8_t* mask, void* stream) {
-  if (l->n == 0) {
-    NB_HIP_CHECK(hipMemsetAsync(mask, 0, (size_t)n, as_stream(stream)));
-    return NB_OK;
-  }
-  return nb_launch_eval(l->dt, l->ptrs_dev, l->n, 0, x, n, mask, nullptr,
-                        nullptr, 0, 0, as_stream(stream));
-}
-
-int nb_first_containing(const nb_boundlist* l, const double* x, int64_t n,
-                        int32_t* idx, void* stream) {
-  if (l->n == 0) {
-    NB_HIP_CHECK(hipMemsetAsync(idx, 0xFF, (size_t)n * 4, as_stream(stream)));
-    return NB_OK;
-  }
-  return nb_launch_eval(l->dt, l->ptrs_dev, l->n, 1, x, n, nullptr, idx,
-                        nullptr, 0, 0, as_stream(stream));
-}
-
-int nb_member_count(const nb_bound* b, const double* x, int64_t n,
-                    uint8_t* count, void* stream) {
-  return nb_launch_eval(b->at.dt, b->self_list_dev, 1, 3, x, n, count, nullptr,
-                        nullptr, 0, 0, as_stream(stream));
-}
-
-int nb_neural_score(const nb_bound* b, const double* x, int64_t n, double* out,
-                    void* stream) {
-  if (b->at.M < 1) {
-    nb_set_error("bound has no neural bound");
-    return NB_ERR_ARG;
-  }
-#ifndef NB_NO_FAST_EVAL
-  if (nb_eval_fast_eligible(b->at.n_dim, b->at.K, b->at.M, b->at.E, false))
-    return nb_launch_eval_fast(b->blob_dev, b->at.n_dim, false, 0, 0, x,
-                               nullptr, n, nullptr, out, 0, 0,
-                               as_stream(stream));
-#endif
-  return nb_launch_eval(b->at.dt, b->self_list_dev, 1, 4, x, n, nullptr,
-                        nullptr, out, 0, 0, as_stream(stream));
-}
-
 // debugging aid: native backtrace on SIGABRT / SIGSEGV (NB_ABORT_TRACE=1)
 static void nb_abort_trace(int sig) {
   void* frames[64];
@@ -300,15 +269,41 @@ static int nb_slice_groups() {
 }
 #define NB_SLICE_GROUPS nb_slice_groups()
 
-int64_t nb_list_eval_work_bytes(const nb_boundlist* l, int64_t n) {
-  const int g = l->n_groups < NB_SLICE_GROUPS ? l->n_groups : NB_SLICE_GROUPS;
+// What a list query walks: the bounds of a list, or one bound as the list of
+// itself
+struct ListView {
+  const double* const* ptrs_dev;
+  int n, dt, n_dim;
+  const int* group_base_dev;
+  const int* group_base;           // host copy, n + 1 entries
+  const FastGroup* groups_dev;
+  int n_groups;
+  const double* blob0;             // any blob of the list (n_dim, strides)
+};
+
+static ListView nb_view_of_list(const nb_boundlist* l) {
+  return {l->ptrs_dev, l->n, l->dt, l->n_dim, l->group_base_dev,
+          l->group_base.data(), l->groups_dev, l->n_groups, l->blob0};
+}
+
+static ListView nb_view_of_bound(const nb_bound* b) {
+  return {b->self_list_dev, 1, b->at.dt, b->at.n_dim, b->group_base_dev,
+          b->group_base, b->groups_dev, b->n_groups, b->blob_dev};
+}
+
+static int64_t nb_view_work_bytes(const ListView& v, int64_t n) {
+  const int g = v.n_groups < NB_SLICE_GROUPS ? v.n_groups : NB_SLICE_GROUPS;
   // (a slice never splits a bound: allow for the largest bound's groups)
   int most = 0;
-  for (int i = 0; i < l->n; ++i) {
-    const int k = l->group_base[i + 1] - l->group_base[i];
+  for (int i = 0; i < v.n; ++i) {
+    const int k = v.group_base[i + 1] - v.group_base[i];
     most = k > most ? k : most;
   }
-  return nb_cand_work_bytes(l->dt, 0, n, (g > most ? g : most) + 1);
+  return nb_cand_work_bytes(v.dt, 0, n, (g > most ? g : most) + 1);
+}
+
+int64_t nb_list_eval_work_bytes(const nb_boundlist* l, int64_t n) {
+  return nb_view_work_bytes(nb_view_of_list(l), n);
 }
 
 int64_t nb_accept_staged_work_bytes(const nb_bound* b, int64_t n) {
@@ -384,6 +379,34 @@ class StageTimer {
   double* hu_ = nullptr;
 };
 
+// The two stages over a non-empty view, in slices of at most NB_SLICE_GROUPS
+// groups each: status bytes, and with mode 1 the first containing bound, as
+// nb_list_eval documents them.  `work`: nb_view_work_bytes(v, n) bytes.
+static int nb_view_eval(const ListView& v, int mode, const double* x,
+                        int64_t n, uint8_t* st, int32_t* first, void* work,
+                        hipStream_t stream) {
+  int b0 = 0;
+  while (b0 < v.n) {
+    int b1 = b0 + 1;
+    while (b1 < v.n && v.group_base[b1 + 1] - v.group_base[b0] <=
+                           NB_SLICE_GROUPS)
+      ++b1;
+    const int g0 = v.group_base[b0], ng = v.group_base[b1] - g0;
+    int *dense = nullptr, *totals = nullptr;
+    long long n_pad = 0;
+    int rc = nb_launch_cand(v.dt, v.n_dim, v.ptrs_dev + b0,
+                            v.group_base_dev + b0, b1 - b0, ng, b0, g0,
+                            b0 > 0 ? 1 : 0, mode, x, n, st, first, (int*)work,
+                            0, 0, &dense, &totals, &n_pad, stream);
+    if (rc != NB_OK) return rc;
+    rc = nb_stage_two(v.blob0, v.n_dim, 1, x, v.groups_dev + g0, ng, totals,
+                      dense, n_pad, n, mode, st, first, stream);
+    if (rc != NB_OK) return rc;
+    b0 = b1;
+  }
+  return NB_OK;
+}
+
 int nb_list_eval(const nb_boundlist* l, int32_t mode, const double* x,
                  int64_t n, uint8_t* st, int32_t* first, void* work,
                  int64_t work_bytes, void* stream) {
@@ -409,27 +432,8 @@ int nb_list_eval(const nb_boundlist* l, int32_t mode, const double* x,
                  (long long)nb_list_eval_work_bytes(l, n));
     return NB_ERR_ARG;
   }
-  // slices of the list with at most NB_SLICE_GROUPS groups each
-  int b0 = 0;
-  while (b0 < l->n) {
-    int b1 = b0 + 1;
-    while (b1 < l->n && l->group_base[b1 + 1] - l->group_base[b0] <=
-                            NB_SLICE_GROUPS)
-      ++b1;
-    const int g0 = l->group_base[b0], ng = l->group_base[b1] - g0;
-    int *dense = nullptr, *totals = nullptr;
-    long long n_pad = 0;
-    int rc = nb_launch_cand(l->dt, l->n_dim, l->ptrs_dev + b0, l->group_base_dev + b0,
-                            b1 - b0, ng, b0, g0, b0 > 0 ? 1 : 0, mode, x, n,
-                            st, first, (int*)work, 0, 0, &dense, &totals,
-                            &n_pad, as_stream(stream));
-    if (rc != NB_OK) return rc;
-    rc = nb_stage_two(l->blob0, l->n_dim, 1, x, l->groups_dev + g0, ng, totals,
-                      dense, n_pad, n, mode, st, first, as_stream(stream));
-    if (rc != NB_OK) return rc;
-    b0 = b1;
-  }
-  return NB_OK;
+  return nb_view_eval(nb_view_of_list(l), mode, x, n, st, first, work,
+                      as_stream(stream));
 }
 
 int nb_accept_staged(const nb_bound* b, uint64_t seed, uint64_t offset,
@@ -461,6 +465,121 @@ int nb_accept_staged(const nb_bound* b, uint64_t seed, uint64_t offset,
   return rc;
 }
 
+// ---- queries without a work argument ---------------------------------------
+// nb_contains, nb_contains_any, nb_first_containing and nb_accept run the same
+// two stages in work space allocated and freed in stream order on the
+// caller's stream (nothing owned by a handle: streams may share one).
+static int nb_scratch_alloc(void** out, int64_t bytes, const char* instead,
+                            hipStream_t stream) {
+  const hipError_t e = hipMallocAsync(out, (size_t)bytes, stream);
+  if (e == hipSuccess) return NB_OK;
+  (void)hipGetLastError();
+  nb_set_error("%lld bytes of stream-ordered work space: %s (%s takes "
+               "caller-owned work space)", (long long)bytes,
+               hipGetErrorString(e), instead);
+  return NB_ERR_HIP;
+}
+
+static int nb_scratch_free(void* work, int rc, hipStream_t stream) {
+  const hipError_t e = hipFreeAsync(work, stream);
+  if (rc == NB_OK && e != hipSuccess) {
+    nb_set_error("hipFreeAsync failed: %s", hipGetErrorString(e));
+    return NB_ERR_HIP;
+  }
+  return rc;
+}
+
+// mask != NULL: mask[i] = 1 if any bound of the view contains row i, else 0;
+// idx != NULL: idx[i] = first bound that contains row i, -1 if none
+static int nb_view_query(const ListView& v, const double* x, int64_t n,
+                         uint8_t* mask, int32_t* idx, hipStream_t stream) {
+  if (n <= 0) return NB_OK;
+  if (v.n == 0) {
+    if (mask != nullptr) NB_HIP_CHECK(hipMemsetAsync(mask, 0, (size_t)n, stream));
+    if (idx != nullptr)
+      NB_HIP_CHECK(hipMemsetAsync(idx, 0xFF, (size_t)n * 4, stream));
+    return NB_OK;
+  }
+  // (a query for the first bound alone: its status bytes live behind the
+  // work space, in whole 32-bit words -- the first stage may OR into the word
+  // that holds a byte)
+  const int64_t work_bytes = nb_view_work_bytes(v, n);
+  const int64_t st_bytes = mask == nullptr ? (n + 3) / 4 * 4 : 0;
+  void* work = nullptr;
+  int rc = nb_scratch_alloc(&work, work_bytes + st_bytes, "nb_list_eval",
+                            stream);
+  if (rc != NB_OK) return rc;
+  uint8_t* st = mask != nullptr ? mask : (uint8_t*)work + work_bytes;
+  rc = nb_view_eval(v, idx != nullptr ? 1 : 0, x, n, st, idx, work, stream);
+  if (rc == NB_OK) {
+    hipLaunchKernelGGL(nb_query_out_kernel, dim3((unsigned)((n + 255) / 256)),
+                       dim3(256), 0, stream, mask, idx, (long long)n);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+      nb_set_error("nb_query_out_kernel: %s", hipGetErrorString(e));
+      rc = NB_ERR_HIP;
+    }
+  }
+  return nb_scratch_free(work, rc, stream);
+}
+
+int nb_contains(const nb_bound* b, const double* x, int64_t n, uint8_t* mask,
+                void* stream) {
+  return nb_view_query(nb_view_of_bound(b), x, n, mask, nullptr,
+                       as_stream(stream));
+}
+
+int nb_contains_any(const nb_boundlist* l, const double* x, int64_t n,
+                    uint8_t* mask, void* stream) {
+  return nb_view_query(nb_view_of_list(l), x, n, mask, nullptr,
+                       as_stream(stream));
+}
+
+int nb_first_containing(const nb_boundlist* l, const double* x, int64_t n,
+                        int32_t* idx, void* stream) {
+  return nb_view_query(nb_view_of_list(l), x, n, nullptr, idx,
+                       as_stream(stream));
+}
+
+int nb_accept(const nb_bound* b, uint64_t seed, uint64_t offset,
+              const double* x, int64_t n, uint8_t* flags, void* stream) {
+  // one neural bound, at most one outer member: the pipelined kernel
+  if (nb_eval_fast_eligible(b->at.n_dim, b->at.K, b->at.M, b->at.E, true))
+    return nb_launch_eval_fast(b->blob_dev, b->at.n_dim, true, 0, 0, x,
+                               nullptr, n, flags, nullptr, seed, offset,
+                               as_stream(stream));
+  if (n <= 0) return NB_OK;
+  const int64_t work_bytes = nb_accept_staged_work_bytes(b, n);
+  void* work = nullptr;
+  int rc = nb_scratch_alloc(&work, work_bytes, "nb_accept_staged",
+                            as_stream(stream));
+  if (rc != NB_OK) return rc;
+  rc = nb_accept_staged(b, seed, offset, x, n, flags, work, work_bytes,
+                        nullptr, stream);
+  return nb_scratch_free(work, rc, as_stream(stream));
+}
+
+int nb_member_count(const nb_bound* b, const double* x, int64_t n,
+                    uint8_t* count, void* stream) {
+  return nb_launch_geom(b->blob_dev, b->at.dt, 1, x, n, nullptr, count,
+                        as_stream(stream));
+}
+
+int nb_neural_score(const nb_bound* b, const double* x, int64_t n, double* out,
+                    void* stream) {
+  if (b->at.M < 1) {
+    nb_set_error("bound has no neural bound");
+    return NB_ERR_ARG;
+  }
+  // with emulators the pipelined kernel, without them the quadratic form alone
+  if (nb_eval_fast_eligible(b->at.n_dim, b->at.K, b->at.M, b->at.E, false))
+    return nb_launch_eval_fast(b->blob_dev, b->at.n_dim, false, 0, 0, x,
+                               nullptr, n, nullptr, out, 0, 0,
+                               as_stream(stream));
+  return nb_launch_geom(b->blob_dev, b->at.dt, 0, x, n, out, nullptr,
+                        as_stream(stream));
+}
+
 int nb_neural_score_rows(const nb_bound* b, int32_t m, int32_t recentre,
                          const double* x, const int64_t* idx, int64_t n,
                          double* out, void* stream) {
@@ -482,19 +601,6 @@ int nb_propose(const nb_bound* b, uint64_t seed, uint64_t offset, int64_t n,
   }
   return nb_launch_draw(b->blob_dev, b->at.n_dim, seed, offset, n, x,
                         as_stream(stream));
-}
-
-int nb_accept(const nb_bound* b, uint64_t seed, uint64_t offset,
-              const double* x, int64_t n, uint8_t* flags, void* stream) {
-#ifndef NB_NO_FAST_EVAL
-  // one neural bound, at most one outer member: the pipelined kernel
-  if (nb_eval_fast_eligible(b->at.n_dim, b->at.K, b->at.M, b->at.E, true))
-    return nb_launch_eval_fast(b->blob_dev, b->at.n_dim, true, 0, 0, x,
-                               nullptr, n, flags, nullptr, seed, offset,
-                               as_stream(stream));
-#endif
-  return nb_launch_eval(b->at.dt, b->self_list_dev, 1, 2, x, n, flags, nullptr,
-                        nullptr, seed, offset, as_stream(stream));
 }
 
 int nb_set_eval_counters(uint64_t* counters_dev) {

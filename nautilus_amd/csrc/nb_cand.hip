@@ -66,15 +66,13 @@ struct CandArgs {
   long long n_pad;
   int chunk, n_waves;
   unsigned long long seed, offset;
-  unsigned long long* counters; // optional, as in nb_eval.hip
+  unsigned long long* counters; // optional: nb_eval_counters()
   // long lists over few rows: blockIdx.y owns the bounds [y * b_chunk,
   // (y + 1) * b_chunk) of the slice (0: one block row walks them all).  The
   // blocks of a row range then share its status bytes / first-bound words:
   // the launcher has initialised them, the kernel only ever ORs / MINs
   int b_chunk;
 };
-
-#define MFMA4(a, b, c) __builtin_amdgcn_mfma_f64_4x4x4f64((a), (b), (c), 0, 0, 0)
 
 // the k-steps of a lower-triangular ellipsoid transform in execution order.
 // SMALL: the last row tile holds at most four real rows (n_dim mod 16 in
@@ -612,8 +610,6 @@ int launch_cand_t(const CandArgs& a, bool small, hipStream_t stream) {
 }
 
 }  // namespace
-
-unsigned long long* nb_eval_counters();
 
 // Tiles per wavefront: two share every A operand.  Proposals: two at any
 // n_dim; lists (first-hit bookkeeping, sphere pre-test, periodic shift next to

@@ -2,8 +2,9 @@
 // the case NautilusBound.sample spends its time in (nautilus.py:193-244: a
 // proposal from the outer union is kept if the neural bound contains it,
 // bounds/neural.py:115-126) -- as a software pipeline over the 128-point
-// passes of a workgroup.  Same arithmetic as nb_eval.hip (bit-identical
-// scores), different schedule:
+// passes of a workgroup (layer arithmetic and operand mapping: nb_mlp.h;
+// ellipsoid stage: same summation order as nb_tile.h's ell_eval, r2 is
+// bit-identical):
 //
 //  * EIGHT wavefronts x one 16-point tile (two wavefronts per SIMD, 256
 //    registers each, no spills up to n_dim = 63): while one wavefront of a
@@ -11,8 +12,8 @@
 //    prologue, the other feeds the matrix pipe.  (Four wavefronts x two tiles
 //    -- every A operand shared by two tiles, one wavefront per SIMD -- reached
 //    0.66 of the fp64 MFMA peak at n_dim = 50; this shape reaches 0.74, and
-//    0.70 at n_dim = 100 where the four-wavefront kernel of nb_eval.hip gets
-//    0.37.)  The weight stream sets the pace -- 66 to 101 tiles per network
+//    0.70 at n_dim = 100 where the four-wavefront shape got 0.37.)  The
+//    weight stream sets the pace -- 66 to 101 tiles per network
 //    against ~12 B/clk of DMA a CU sustains -- so a staged weight byte has to
 //    serve as many points as the registers allow: 128 per pass.
 //  * two LDS regions of 38 tiles alternate between feeding the matrix cores
@@ -29,9 +30,10 @@
 //  * the layers of a stage run as one operand pipeline with the weight DMA of
 //    the next stage sliced into the k-steps (nb_mlp.h).
 //
-// Eligible: n_dim <= 128, one neural bound with E >= 1 networks, MODE_SAMPLE
-// with at most one outer member or MODE_SCORE; everything else goes through
-// nb_eval.hip.
+// Eligible (nb_eval_fast_eligible): n_dim <= 128, E >= 1 networks; proposals
+// with one neural bound and at most one outer member, scores of any neural
+// bound.  Other proposals take the two stages (nb_cand.hip + BATCH), the
+// quadratic form of a bound without emulators nb_geom.hip.
 #include "nb_common.h"
 #include "nb_launch.h"
 
@@ -56,7 +58,7 @@ struct FastArgs {
   double* out_f64;
   unsigned long long seed;
   unsigned long long offset;
-  unsigned long long* counters;   // optional, as in nb_eval.hip
+  unsigned long long* counters;   // optional: nb_eval_counters()
   // BATCH (second stage of nb_cand.hip): the candidates of ALL (bound, neural
   // bound) groups of a query in one launch.  Group g owns the rows
   // dense[g * n_pad ... + totals[g]); a 128-point pass belongs to one group.
@@ -113,7 +115,7 @@ __device__ __forceinline__ void ell_eval_centre(
         const double a =
             tiles[(ht * (ht + 1) / 2 + kt) * NB_TILE + s * 64 + lane4];
 #pragma unroll
-        for (int t = 0; t < T; ++t) r4[t] = NB_MFMA4(a, d[t][ks], r4[t]);
+        for (int t = 0; t < T; ++t) r4[t] = MFMA4(a, d[t][ks], r4[t]);
       }
 #pragma unroll
       for (int t = 0; t < T; ++t) {
@@ -660,8 +662,6 @@ int launch_fast(const FastArgs& a, hipStream_t stream) {
 }
 
 }  // namespace
-
-unsigned long long* nb_eval_counters();
 
 // one neural bound with networks, and for proposals at most one outer member
 // (the draw then needs no overlap count)

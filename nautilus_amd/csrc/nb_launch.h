@@ -28,11 +28,15 @@ int nb_launch_eval_fast_batch(const double* blob0_dev, int n_dim, int recentre,
                               long long n_upper, int out_mode,
                               unsigned char* st, int* first,
                               hipStream_t stream);
-int nb_launch_eval(int dt, const double* const* blobs_dev, int nb, int mode,
-                   const double* x, long long n, unsigned char* out_u8,
-                   int* out_i32, double* out_f64, unsigned long long seed,
-                   unsigned long long offset, hipStream_t stream);
+// count = 0: out_f64[2 i] = r2 against neural bound 0, out_f64[2 i + 1] = 0;
+// count = 1: out_u8[i] = outer members containing row i (nb_geom.hip)
+int nb_launch_geom(const double* blob_dev, int dt, int count, const double* x,
+                   long long n, double* out_f64, unsigned char* out_u8,
+                   hipStream_t stream);
+// optional device counters of the bound evaluation (nb_api.hip): [0] outer
+// member, [1] neural ellipsoid, [2] emulator point evaluations; null = off
 void nb_eval_set_counters(unsigned long long* dev);
+unsigned long long* nb_eval_counters();
 int nb_launch_draw(const double* blob_dev, int n_dim, unsigned long long seed,
                    unsigned long long offset, long long n, double* x_out,
                    hipStream_t stream);

@@ -43,10 +43,10 @@
 // feature 8 (ks / 2) + 2 lg + ks % 2.
 //
 // Header, CDF, ulo / uhi (the unit cube of a union, slot order, -+inf where
-// not boxed): nb_eval.hip, nb_cand.hip, nb_eval_fast.hip, nb_kernels.hip.
+// not boxed): nb_geom.hip, nb_cand.hip, nb_eval_fast.hip, nb_kernels.hip.
 //
 // Ell block (member of the outer union, or ellipsoid of a neural bound); read
-// by nb_eval.hip, nb_cand.hip, nb_eval_fast.hip and nb_transform.hip:
+// by nb_geom.hip, nb_cand.hip, nb_eval_fast.hip and nb_transform.hip:
 //   [0]            n_ell (as int64 bits; 0 => pure cube member, no MFMA work)
 //   [1]            members: 1 if any limit is finite, else 0 (int64 bits);
 //                  neural bounds: the squared bounding radius (a double)
@@ -59,7 +59,7 @@
 //                  sl = nb_slot_of_feature(k), ks = sl / 4, lg = sl % 4 the
 //                  element lives in tile (ks / 4, h / 16) at
 //                  (ks % 4) * 64 + lg * 16 + h % 16
-// Neural block = ell block, then (nb_eval.hip, nb_eval_fast.hip):
+// Neural block = ell block, then (nb_eval_fast.hip):
 //   thr, pad       score_predict_min - 1e-9 (bounds/neural.py:125)
 //   mean[DP], inv_scale[DP]   in feature order (0 and 1 beyond D)
 //   E nets, each: L1 tiles [KT1][7], L2 [7][4], L3 [4][2], L4 [2][1];
@@ -85,7 +85,7 @@ enum {
   NB_H_NET_STRIDE, NB_H_KT1, NB_H_TOTAL, NB_H_OFF_STREAM, NB_H_OFF_SHIFT
 };
 
-// K permutation of the ellipsoid stage (nb_eval.hip / nb_stream.hip): slot
+// K permutation of the ellipsoid stage (nb_tile.h / nb_stream.hip): slot
 // (ks, lg) <-> feature 8*(ks>>1) + 2*lg + (ks&1).
 constexpr int nb_slot_of_feature(int f) {
   return 4 * (2 * (f >> 3) + (f & 1)) + ((f & 7) >> 1);

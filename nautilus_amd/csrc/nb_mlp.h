@@ -1,25 +1,45 @@
-// Dense emulator layers on v_mfma_f64_16x16x4_f64 as ONE operand pipeline per
-// stage (used by nb_eval_fast.hip): rows = output units, cols = the 16 points
-// of a tile, K = input units; weights as A operands from tile-major LDS
-// storage, activations as B operands in registers (the C/D layout of a layer
-// is the B layout of the next one).
+// Dense emulator layers on the matrix cores as ONE operand pipeline per stage
+// (used by nb_eval_fast.hip): out[h] = act(sum_k in[k] W[k][h]) for the T
+// tiles of 16 points a wavefront holds.
 //
-// Differences to the layer code of nb_eval.hip:
+// Operand mapping on v_mfma_f64_16x16x4_f64: rows i = output units, cols j =
+// the 16 points of the tile, K = input units.  Lane l holds for point (l & 15)
+// the inputs 4 ks + (l >> 4), ks = 0, 1, ... (one B operand per k-step).  The
+// C/D layout (col = l & 15, row = (l >> 4) + 4 reg) is exactly the B-operand
+// layout of the next layer, so activations never leave the registers between
+// layers.  Weights are A operands from 16x16 tile-major storage in LDS
+// (nb_layout.h): one contiguous 512-byte row of a tile per MFMA, conflict-free
+// ds_read_b64.  The bias is row k = K of the weights; the input carries a
+// constant 1 there (fl_pad writes it for the next layer).
+//
+// The hidden sizes (100, 50, 20, 1) leave 4, 2, 4 and 1 units in the last
+// 16-wide tile of a layer.  Those run on v_mfma_f64_4x4x4_4b_f64 instead of a
+// full tile: four 4x4x4 blocks = the same 4 units for 4 x 4 points, 16 cycles
+// instead of 64.  Register layout (measured on gfx950): A lane i + 4 b + 16 k,
+// B lane p + 16 k, D lane p + 16 i with p = 4 b + j -- the B operand is the
+// one of the 16x16x4 instruction and D is its register 0, so the result is
+// directly k-step 4 (HT - 1) of the next layer.  The A operand is gathered
+// from the unchanged tile-major weights (fl_read_a: element (kk, hh) of the
+// last tile, hh = lane & 3).
+//
+// Schedule.  A layer is cut into blocks of SPLIT output tiles (fewer live
+// accumulators per block, more operand reuse within it); inside a block the
+// k-steps are the outer loop and the block's tiles the inner one, so every B
+// operand meets all A operands of its k-step and the accumulators are
+// independent.  Only the last NGUARD k-steps depend on the runtime input
+// count; the others form one basic block.  On top of that:
 //  * the A operands of the first k-step of a block are read by the block
 //    BEFORE it (during its last k-step), across block and layer boundaries,
-//    so the LDS latency is exposed once per stage instead of once per block;
+//    so the LDS latency is exposed once per stage, not once per block;
 //  * ReLU is applied by the consumer (one v_max_f64 per B operand and k-step,
-//    hidden behind the MFMAs) instead of by the producer at the end of a
-//    block, where it had to wait for the matrix pipe to drain;
-//  * the weight DMA of the next stage is sliced into the k-steps (`tick`)
-//    instead of being issued in one burst at the start of the stage, where
-//    the 64 B/clk fill path of the CU stalled the issuing wavefronts.
-// Summation order per output unit is unchanged (k-steps ascending), so the
-// results are bit-identical to nb_eval.hip's.
+//    hidden behind the MFMAs): a producer applying it at the end of a block
+//    would wait for the matrix pipe to drain;
+//  * the weight DMA of the next stage is sliced into the k-steps (`tick`):
+//    issued in one burst at the start of a stage it stalls the issuing
+//    wavefronts on the 64 B/clk fill path of the CU.
+// Summation order per output unit: k-steps ascending, one accumulator.
 #pragma once
 #include "nb_tile.h"
-
-#define NB_MFMA4(a, b, c) __builtin_amdgcn_mfma_f64_4x4x4f64((a), (b), (c), 0, 0, 0)
 
 namespace {
 
@@ -88,7 +108,7 @@ __device__ __forceinline__ void fl_block(
       for (int t = 0; t < T; ++t) acc[t][h] = MFMA(a[h], b[t], acc[t][h]);
     if constexpr (REM) {
 #pragma unroll
-      for (int t = 0; t < T; ++t) rem[t] = NB_MFMA4(a[NF], b[t], rem[t]);
+      for (int t = 0; t < T; ++t) rem[t] = MFMA4(a[NF], b[t], rem[t]);
     }
   };
   // a use of the operands: the compiler's s_waitcnt lands here, before the
@@ -167,7 +187,7 @@ __device__ __forceinline__ void fl_chunk(
       for (int t = 0; t < T; ++t)
         acc[t][h] = MFMA(a[h], in[t][ks], acc[t][h]);
 #pragma unroll
-    for (int t = 0; t < T; ++t) rem[t] = NB_MFMA4(a[NF], in[t][ks], rem[t]);
+    for (int t = 0; t < T; ++t) rem[t] = MFMA4(a[NF], in[t][ks], rem[t]);
   };
   auto arrived = [&](const double (&a)[NA]) __attribute__((always_inline)) {
 #pragma unroll

@@ -1,10 +1,13 @@
-// MFMA tile helpers shared by the bound-evaluation kernel (nb_eval.hip) and
-// the MVEE kernel (nb_mvee.hip): the B-operand block of 16-point tiles and the
-// ellipsoid transform y = B_inv (x - c) on v_mfma_f64_16x16x4_f64.
+// MFMA tile helpers shared by the bound-evaluation kernels (nb_geom.hip,
+// nb_cand.hip, nb_eval_fast.hip), the transform and the MVEE kernel
+// (nb_transform.hip, nb_mvee.hip): the B-operand block of 16-point tiles and
+// the ellipsoid transform y = B_inv (x - c) on v_mfma_f64_16x16x4_f64.
 #pragma once
 #include "nb_common.h"
 
+// v_mfma_f64_16x16x4_f64 and v_mfma_f64_4x4x4_4b_f64 (device code)
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
+#define MFMA4(a, b, c) __builtin_amdgcn_mfma_f64_4x4x4f64((a), (b), (c), 0, 0, 0)
 
 namespace {
 

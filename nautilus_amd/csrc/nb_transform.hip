@@ -3,7 +3,7 @@
 // nautilus/neural.py:74-77 mean / scale / (x - mean) / scale).  The transform
 // runs through the same matrix-core tile code as contains() and the emulator
 // evaluation (nb_tile.h), so the network is trained on exactly the inputs it
-// later sees inside nb_eval_kernel.
+// later sees inside nb_eval_fast_kernel.
 #include "nb_tile.h"
 #include "nb_launch.h"
 #include "../../include/nautilus_hip.h"

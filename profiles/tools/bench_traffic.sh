@@ -1,7 +1,7 @@
-# HBM traffic of nb_eval_kernel over the timed region of the default bench.py
+# HBM traffic of nb_eval_fast_kernel over the timed region of the default bench.py
 # run: FETCH_SIZE and WRITE_SIZE in separate rocprofv3 --pmc passes (kernel
 # trace only, as MI355X_MICROARCH.md prescribes); the timed region's launches
-# are the last `roofline.launches` nb_eval_kernel dispatches of the run.
+# are the last `roofline.launches` nb_eval_fast_kernel dispatches of the run.
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$PWD}
 cd /tmp
@@ -18,7 +18,7 @@ for c in ('FETCH_SIZE', 'WRITE_SIZE'):
     n = line['roofline']['launches']
     f = glob.glob('/tmp/bt_%s/*counter_collection.csv' % c)[0]
     rows = [r for r in csv.DictReader(open(f))
-            if 'nb_eval_kernel' in r['Kernel_Name'] and r['Counter_Name'] == c]
+            if 'nb_eval_fast_kernel' in r['Kernel_Name'] and r['Counter_Name'] == c]
     rows.sort(key=lambda r: int(r['Dispatch_Id']))
     vals = [float(r['Counter_Value']) for r in rows[-n:]]
     out[c] = dict(launches=n, mean_kb=sum(vals) / len(vals),
@@ -26,7 +26,7 @@ for c in ('FETCH_SIZE', 'WRITE_SIZE'):
 # FETCH_SIZE counts 64-byte units as "KB/2" on gfx950 (x2 correction)
 read_b = out['FETCH_SIZE']['mean_kb'] * 1024 * 2
 write_b = out['WRITE_SIZE']['mean_kb'] * 1024
-res = dict(kernel='nb_eval_kernel', command='python bench.py --no-cpu-baseline',
+res = dict(kernel='nb_eval_fast_kernel', command='python bench.py --no-cpu-baseline',
            launches=out['FETCH_SIZE']['launches'],
            hbm_read_bytes_per_launch=read_b, hbm_write_bytes_per_launch=write_b,
            hbm_bytes_per_launch=read_b + write_b, raw=out)

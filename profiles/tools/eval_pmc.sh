@@ -10,7 +10,7 @@ import csv, glob, sys
 c = sys.argv[1]
 fs = glob.glob('/tmp/pm_%s/*counter_collection.csv' % c)
 if not fs: print(c, 'no data'); sys.exit()
-vals = [float(r['Counter_Value']) for r in csv.DictReader(open(fs[0])) if 'nb_eval_kernel' in r['Kernel_Name'] and r['Counter_Name'] == c]
+vals = [float(r['Counter_Value']) for r in csv.DictReader(open(fs[0])) if 'nb_eval_fast_kernel' in r['Kernel_Name'] and r['Counter_Name'] == c]
 print(c, 'launches', len(vals), 'mean %.4g' % (sum(vals)/max(1,len(vals))))
 PY
 done
