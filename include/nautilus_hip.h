@@ -181,7 +181,9 @@ int nb_compact_rows(const double* x_dev, const uint8_t* flags_dev,
 
 /* Per-shell evidence statistics (sampler.py:927-943): out_dev[0] =
  * logsumexp(log_l), out_dev[1] = logsumexp(2 log_l), out_dev[2] = max,
- * out_dev[3] = number of elements >= threshold (sampler.py:1144).           */
+ * out_dev[3] = number of elements >= threshold (sampler.py:1144).  A NaN
+ * element makes out_dev[0..2] NaN and counts as below the threshold; a +inf
+ * element makes them +inf (numpy's max, scipy's logsumexp).                 */
 int nb_shell_stats(const double* log_l_dev, int64_t n, double threshold,
                    double* out_dev, void* scratch_dev, void* stream);
 int64_t nb_shell_stats_scratch_bytes(int64_t n);
@@ -203,7 +205,9 @@ int64_t nb_shell_stats_scratch_bytes(int64_t n);
  *   nb_live_stats    for one shell's log L: out_dev[0] = #(l > threshold),
  *                    out_dev[1] = logsumexp(l | l > threshold), out_dev[2] =
  *                    #(l == threshold) -- the shell's share of the live
- *                    weight (shuffle reductions).                            */
+ *                    weight (shuffle reductions); a +inf above the threshold
+ *                    makes out_dev[1] +inf, a NaN is neither above nor at
+ *                    the threshold.                                          */
 int nb_live_append(const double* log_l_dev, int64_t n, const double* thr_dev,
                    double* pool_dev, int32_t* pool_n_dev, int32_t capacity,
                    int32_t* overflow_dev, void* stream);

@@ -338,6 +338,11 @@ __device__ inline Lse lse_merge(Lse a, Lse b) {
   Lse o;
   o.m = fmax(a.m, b.m);
   o.cnt = a.cnt + b.cnt;
+  // a NaN element makes the maximum and both sums NaN (fmax would drop it),
+  // a +inf element makes them +inf (exp(inf - inf) is NaN): numpy's max and
+  // scipy's logsumexp
+  if (a.m != a.m || b.m != b.m) { o.m = o.s1 = o.s2 = NAN; return o; }
+  if (o.m == INFINITY) { o.s1 = o.s2 = INFINITY; return o; }
   if (o.m == -INFINITY) { o.s1 = 0.0; o.s2 = 0.0; return o; }
   const double ea = (a.m == -INFINITY) ? 0.0 : exp(a.m - o.m);
   const double eb = (b.m == -INFINITY) ? 0.0 : exp(b.m - o.m);

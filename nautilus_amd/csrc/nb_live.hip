@@ -110,6 +110,8 @@ __device__ __forceinline__ LvAcc lv_merge(LvAcc a, LvAcc b) {
   o.gt = a.gt + b.gt;
   o.eq = a.eq + b.eq;
   if (o.m == -__builtin_huge_val()) { o.s = 0.0; return o; }
+  // a +inf above the threshold: the sum is +inf (exp(inf - inf) is NaN)
+  if (o.m == __builtin_huge_val()) { o.s = o.m; return o; }
   o.s = (a.m == -__builtin_huge_val() ? 0.0 : a.s * exp(a.m - o.m)) +
         (b.m == -__builtin_huge_val() ? 0.0 : b.s * exp(b.m - o.m));
   return o;

@@ -1336,6 +1336,7 @@ def test_shell_exclusion_and_association(dev, nautilus_d4, neural_d4):
 
 
 def test_compaction_edge_cases(dev):
+    """(Masks, flips, scan rounds and sentinels: test_stream_ops_gpu.py.)"""
     import torch
     gen = torch.Generator(device='cuda').manual_seed(0)
     for n, d in [(1, 3), (2047, 5), (2048, 50), (2049, 7), (100000, 20)]:
@@ -1353,6 +1354,7 @@ def test_compaction_edge_cases(dev):
 
 
 def test_shell_stats_match_reference(dev):
+    """(Size edges, thresholds, NaN and +inf: test_stream_ops_gpu.py.)"""
     import torch
     from scipy.special import logsumexp
     g = load_golden('shellstats')
