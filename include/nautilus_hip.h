@@ -755,6 +755,55 @@ int nb_gps_loglike(const nb_gps* h, const double* model_dev, int64_t ld,
                    double* out_dev, void* stream);
 int nb_gps_destroy(nb_gps* h);
 
+/* The same series likelihood (sampler.py:863-873) for a covariance that is a
+ * SUM of n_terms = 2..NB_GPS_MAX_TERMS of the kernels above,
+ *   K_i[j,k] = sum_I a_iI rho_I(|t_j - t_k| / l_iI) + delta_jk (sigma2_j + s_i),
+ * such as two oscillators at P and P / 2 or red noise plus a quasi-periodic
+ * term.  nb_gps_create_terms takes the kernel codes kernels[0..n_terms) in the
+ * caller's order and otherwise the arguments of nb_gps_create (whose checks
+ * of n_data, t, data, sigma2 and log_norm it repeats with their messages); it
+ * returns the same handle type, which nb_gps_loglike and nb_gps_destroy
+ * serve.  The states of the terms (1, 2, 3, 2 as above) add up to at most
+ * NB_GPS_MAX_STATES: 10 pairs and 13 triples up to order.  NB_ERR_ARG, each
+ * with a message of its own: a NULL kernels, t, data or out; n_terms outside
+ * 2..NB_GPS_MAX_TERMS (one term is nb_gps_create); a code outside NB_GPS_EXP
+ * .. NB_GPS_SHO; more than NB_GPS_MAX_STATES states.
+ * Row i of the hyper input holds, for every term in the caller's order,
+ * (a, l) or for NB_GPS_SHO (a, l, q), and in one last column s: W = sum w_I +
+ * 1 <= 10 doubles, and nb_gps_loglike asks ld_hyper >= W of such a handle.
+ * Inside, the terms sit in SLOTS sorted by kernel code, equal codes in the
+ * caller's order, and the kernel is told the column of every slot: reordering
+ * the codes together with their columns changes no bit.  Slot I has R_I
+ * states from index o_I on, S = sum R_I, the transition Phi_I of its kernel at
+ * r_I = min(dt / l_I, 1e4) and the first column p_I of its stationary
+ * covariance over a_I ([1], [1, 0], [1, 0, -1/3], [1, 0]).  With A = sum_I a_I
+ * in slot order, G = 0 (S x S, symmetric) and g = 0, step n is
+ *   1. G_IJ <- Phi_I G_IJ Phi_J^T block by block, lower blocks only, T =
+ *      Phi_I G_IJ first and every sum in index order; g_I <- Phi_I g_I
+ *   2. Gh[i] = sum_J G[i][o_J]; c = sum_I Gh[o_I]; noise = sigma2_n + s;
+ *      d = (A - c) + noise
+ *   3. v = (m_n - d_n) - sum_I g[o_I]; the row is flagged when m_n is not
+ *      finite or d is outside (0, +inf)
+ *   4. u[i] = a_I p_I[i - o_I] - Gh[i]; k = u (1 / d), the reciprocal an
+ *      estimate with two Newton steps
+ *   5. g <- g + k v; G <- G + u k^T on the lower triangle, mirrored
+ *   6. Q += v^2 / d as a compensated sum; log d through the product of the
+ *      mantissas and the sum of the exponents, renormalised every 256 steps
+ * and out_dev[i] = log_norm - (Q + L) / 2 (nb_gps_terms.hip).  A row is NaN,
+ * and changes no other row, with an m_ij that is not finite; any a_I negative
+ * or not finite (a_I = 0 is legal and switches the term off); any l_I outside
+ * (0, +inf); any q_I outside (1/2, +inf); an s negative or not finite; or a
+ * pivot outside (0, +inf).  One difference from a single term: the form G00 =
+ * a - noise k0 that nb_gps.hip uses has no exact analogue for a sum, so a
+ * repeated time with sigma2_j + s = 0 is unspecified here: that row is NaN or
+ * finite, other rows are untouched, and nothing worse happens.             */
+#define NB_GPS_MAX_TERMS 3
+#define NB_GPS_MAX_STATES 6
+int nb_gps_create_terms(int32_t n_data, const double* t, const double* data,
+                        const double* sigma2, int32_t n_terms,
+                        const int32_t* kernels, double log_norm,
+                        nb_gps** out);
+
 
 /* Two-stage evaluation of bounds with several outer members, several neural
  * bounds, or of lists of bounds (bounds/union.py:285-289, 316-319;

@@ -196,6 +196,9 @@ _SIGNATURES = {
     'nb_gp_destroy': (C.c_int, [C.c_void_p]),
     'nb_gps_create': (C.c_int, [C.c_int32, c_double_p, c_double_p, c_double_p,
                                 C.c_int32, C.c_double, C.POINTER(C.c_void_p)]),
+    'nb_gps_create_terms': (C.c_int, [C.c_int32, c_double_p, c_double_p,
+                                      c_double_p, C.c_int32, c_int32_p,
+                                      C.c_double, C.POINTER(C.c_void_p)]),
     'nb_gps_loglike': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64,
                                  C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                  C.c_void_p]),

@@ -911,6 +911,8 @@ struct nb_gps {
   int n_data = 0;
   int kernel = 0;
   double log_norm = 0.0;
+  int width = 0;                                 // doubles of a hyper row
+  nb_gps_plan plan;                              // n_terms 0: one term
 };
 
 int nb_gps_create(int32_t n_data, const double* t, const double* data,
@@ -923,6 +925,25 @@ int nb_gps_create(int32_t n_data, const double* t, const double* data,
   h.n_data = n_data;
   h.kernel = kernel;
   h.log_norm = log_norm;
+  h.width = kernel == NB_GPS_SHO ? 4 : 3;
+  return nb_make_table(rc, image, "Gaussian-process series likelihood", h,
+                       out);
+}
+
+int nb_gps_create_terms(int32_t n_data, const double* t, const double* data,
+                        const double* sigma2, int32_t n_terms,
+                        const int32_t* kernels, double log_norm,
+                        nb_gps** out) {
+  nb_gps h;
+  int rc = plan_gps_terms(n_terms, kernels, t, data, out, &h.plan);
+  if (rc != NB_OK) return rc;
+  std::vector<double> image;
+  rc = pack_gps(n_data, t, data, sigma2, h.plan.kind[0], log_norm, out,
+                &image);
+  h.n_data = n_data;
+  h.kernel = h.plan.kind[0];
+  h.log_norm = log_norm;
+  h.width = h.plan.width;
   return nb_make_table(rc, image, "Gaussian-process series likelihood", h,
                        out);
 }
@@ -937,7 +958,7 @@ int nb_gps_loglike(const nb_gps* h, const double* model, int64_t ld,
                  "handle, n >= 0)");
     return NB_ERR_ARG;
   }
-  const int64_t width = h->kernel == NB_GPS_SHO ? 4 : 3;
+  const int64_t width = h->width;
   if ((n > 1 && (ld < h->n_data || ld_hyper < width)) ||
       (n > 0 && (model == nullptr || hyper == nullptr || out == nullptr))) {
     nb_set_error("bad Gaussian-process series likelihood arguments (ld >= "
@@ -945,6 +966,11 @@ int nb_gps_loglike(const nb_gps* h, const double* model, int64_t ld,
                  (long long)width);
     return NB_ERR_ARG;
   }
+  if (h->plan.n_terms > 1)
+    return nb_launch_gps_terms(h->dev, h->n_data, h->plan.n_terms,
+                               h->plan.kind, h->plan.col, h->plan.col_s,
+                               model, ld, hyper, ld_hyper, n, h->log_norm,
+                               out, as_stream(stream));
   return nb_launch_gps(h->dev, h->n_data, h->kernel, model, ld, hyper,
                        ld_hyper, n, h->log_norm, out, as_stream(stream));
 }

@@ -898,4 +898,75 @@ int pack_gps(int32_t n_data, const double* t, const double* data,
   return NB_OK;
 }
 
+// Where nb_gps_terms.hip finds the terms of a sum: the slots are the terms
+// sorted by kernel code, equal codes in the caller's order; kind[I] is the
+// code of slot I, col[I] the column of its (a, l[, q]) in a row of the hyper
+// input, which holds the terms in the CALLER's order and s in its last column
+// col_s = width - 1.
+struct nb_gps_plan {
+  int n_terms = 0;
+  int kind[NB_GPS_MAX_TERMS] = {0, 0, 0};
+  int col[NB_GPS_MAX_TERMS] = {0, 0, 0};
+  int col_s = 0;
+  int width = 0;
+  int states = 0;
+};
+
+// The checks of nb_gps_create_terms that nb_gps_create does not have, and
+// the plan; pack_gps checks the rest and packs the same image.
+int plan_gps_terms(int32_t n_terms, const int32_t* kernels, const double* t,
+                   const double* data, const void* out, nb_gps_plan* plan) {
+  if (kernels == nullptr || t == nullptr || data == nullptr ||
+      out == nullptr) {
+    nb_set_error("the Gaussian-process series likelihood of a sum of terms "
+                 "needs kernels, t, data and out: no NULL pointer");
+    return NB_ERR_ARG;
+  }
+  if (n_terms < 2 || n_terms > NB_GPS_MAX_TERMS) {
+    nb_set_error("the Gaussian-process series likelihood of a sum takes 2..%d "
+                 "terms, not %d (one term goes through nb_gps_create)",
+                 NB_GPS_MAX_TERMS, (int)n_terms);
+    return NB_ERR_ARG;
+  }
+  nb_gps_plan p;
+  p.n_terms = n_terms;
+  int first[NB_GPS_MAX_TERMS];                   // of a term, caller's order
+  int column = 0;
+  for (int i = 0; i < n_terms; ++i) {
+    if (kernels[i] < NB_GPS_EXP || kernels[i] > NB_GPS_SHO) {
+      nb_set_error("term %d of the Gaussian-process series likelihood has "
+                   "kernel %d: not one of NB_GPS_EXP .. NB_GPS_SHO", i,
+                   (int)kernels[i]);
+      return NB_ERR_ARG;
+    }
+    first[i] = column;
+    column += kernels[i] == NB_GPS_SHO ? 3 : 2;
+    p.states += kernels[i] == NB_GPS_EXP ? 1
+                : kernels[i] == NB_GPS_MATERN52 ? 3 : 2;
+  }
+  if (p.states > NB_GPS_MAX_STATES) {
+    nb_set_error("the terms of the Gaussian-process series likelihood have %d "
+                 "states (exp 1, matern32 2, matern52 3, sho 2): at most %d, "
+                 "in at most %d terms", p.states, NB_GPS_MAX_STATES,
+                 NB_GPS_MAX_TERMS);
+    return NB_ERR_ARG;
+  }
+  p.col_s = column;
+  p.width = column + 1;
+  // a stable insertion sort of at most three
+  int order[NB_GPS_MAX_TERMS] = {0, 1, 2};
+  for (int i = 1; i < n_terms; ++i)
+    for (int j = i; j > 0 && kernels[order[j]] < kernels[order[j - 1]]; --j) {
+      const int swap = order[j];
+      order[j] = order[j - 1];
+      order[j - 1] = swap;
+    }
+  for (int i = 0; i < n_terms; ++i) {
+    p.kind[i] = kernels[order[i]];
+    p.col[i] = first[order[i]];
+  }
+  *plan = p;
+  return NB_OK;
+}
+
 }  // namespace

@@ -854,13 +854,24 @@ GPS_BLOCK = 32                     # NB_GPS_BLOCK of nb_layout.h: the columns
 #                                    of a block nb_gps.hip stages through LDS
 
 
+def gps_width(kernel):
+    """Columns of a hyper row: (a, l, s[, q]) for one kernel name; for a
+    sequence of names (a, l[, q]) per term in its order and s last."""
+    if isinstance(kernel, str):
+        return 4 if kernel == 'sho' else 3
+    return sum(3 if k == 'sho' else 2 for k in kernel) + 1
+
+
 class GPSTable(_Table):
     """Device-resident ordered series of a Gaussian-process likelihood
     evaluated as a filter (``nb_gps_create``): ``t`` (P,) finite and
     non-decreasing, ``data`` (P,) finite, ``sigma2`` (P,) = sigma^2 >= 0
     (None = 0) and ``kernel`` a key of ``GPS_KERNELS``, with ``log_norm``
-    added to every result.  Packed and uploaded once; every ``loglike`` is
-    one launch on the current stream."""
+    added to every result.  ``kernel`` may also be a tuple or list of 2 or 3
+    keys with at most 6 states together (NB_GPS_MAX_STATES): a sum of terms
+    (``nb_gps_create_terms``).  ``width`` is the number of columns of a hyper
+    row.  Packed and uploaded once; every ``loglike`` is one launch on the
+    current stream."""
 
     _destroy = 'nb_gps_destroy'
 
@@ -869,17 +880,27 @@ class GPSTable(_Table):
         self.n_data = p = len(data)
         t = _shape_p(t, p, 't')
         sigma2 = _shape_p(sigma2, p, 'sigma2')
-        if kernel not in GPS_KERNELS:
-            raise ValueError('kernel must be one of %s, not %r' %
-                             (sorted(GPS_KERNELS), kernel))
-        self.width = 4 if kernel == 'sho' else 3
-        self._create('nb_gps_create', p, _dp(t), _dp(data), _dp(sigma2),
-                     GPS_KERNELS[kernel], float(log_norm))
+        terms = [kernel] if isinstance(kernel, str) else list(kernel)
+        for name in terms:
+            if name not in GPS_KERNELS:
+                raise ValueError('kernel must be one of %s, not %r' %
+                                 (sorted(GPS_KERNELS), name))
+        self.width = gps_width(kernel)
+        if isinstance(kernel, str):
+            self._create('nb_gps_create', p, _dp(t), _dp(data), _dp(sigma2),
+                         GPS_KERNELS[kernel], float(log_norm))
+            return
+        # the library refuses a number of terms or of states it does not have
+        codes = np.array([GPS_KERNELS[k] for k in terms], dtype=np.int32)
+        self._create('nb_gps_create_terms', p, _dp(t), _dp(data),
+                     _dp(sigma2), len(codes),
+                     codes.ctypes.data_as(_lib.c_int32_p), float(log_norm))
 
     def loglike(self, model, hyper, ld=None, ld_hyper=None):
         """log L of the rows of the cuda float64 tensors ``model`` (n, P) and
         ``hyper`` ((n, 3) with columns (a, l, s); (n, 4) with a column q for
-        'sho'), both read in place (``_rows_loglike``)."""
+        'sho'; (n, ``width``) with (a, l[, q]) per term and s last for a sum
+        of terms), both read in place (``_rows_loglike``)."""
         n = model.shape[0]
         if hyper.shape[0] != n:
             raise ValueError('model and hyper must have the same number of '

@@ -954,6 +954,9 @@ class GaussianProcessLikelihood(_ModelLikelihood):
 N_GPS_MAX = 1 << 20                # NB_GPS_MAX_DATA of nautilus_hip.h
 GPS_KERNELS = ('exp', 'matern32', 'matern52', 'sho')
 GPS_CAP = 1e4                      # of dt / l, the cap of gp_correlation
+GPS_STATES = {'exp': 1, 'matern32': 2, 'matern52': 3, 'sho': 2}
+GPS_MAX_TERMS = 3                  # NB_GPS_MAX_TERMS of nautilus_hip.h
+GPS_MAX_STATES = 6                 # NB_GPS_MAX_STATES
 
 
 def sho_correlation(r, q):
@@ -1033,7 +1036,28 @@ class GaussianProcessSeriesLikelihood(_ModelLikelihood):
     negative or not finite or, for 'sho', q is outside (1/2, +inf); or when a
     pivot of the recursion -- the predictive variance of a measurement given
     the earlier ones -- is outside (0, +inf).  That changes no bit of any
-    other row."""
+    other row.
+
+    A sum of terms: ``kernel`` may be a tuple or list of 2 or 3 of the names
+    above whose states add up to at most 6 (10 pairs and 13 triples up to
+    order), such as ``('sho', 'sho')`` for stellar rotation at P and P / 2
+    or ``('matern32', 'sho')`` for red noise plus a quasi-periodic term:
+
+        K_jk = sum_i a_i rho_i(|t_j - t_k| / l_i) + delta_jk (sigma_j^2 + s).
+
+    ``h`` is then (n, W) and holds, for every term in the order given,
+    (a_i, l_i) or for 'sho' (a_i, l_i, q_i), and s in one last column: W =
+    sum w_i + 1 <= 10.  The sum is itself a state-space kernel -- the states
+    concatenated, the transition block diagonal -- and the same kind of
+    filter walks it with a state of at most 6 x 6 numbers (nb_gps_terms.hip,
+    whose header states the recursion).  Inside, the terms are sorted by
+    kernel, equal names in their order: naming them in another order together
+    with their columns changes no bit.  The NaN rules hold for every a_i (a_i
+    = 0 is legal and switches the term off), l_i and q_i.  A string keeps the
+    single-term path bit for bit; a sequence of one name is refused.  One
+    difference from a single term: a repeated time with sigma_j^2 + s = 0,
+    which one term answers with a NaN row, is unspecified for a sum -- the
+    row is NaN or finite, and no other row is touched."""
 
     _pair = True
     _what = 'the model output and the hyper-parameters'
@@ -1041,13 +1065,38 @@ class GaussianProcessSeriesLikelihood(_ModelLikelihood):
     def __init__(self, model, t, data, sigma=None, *, kernel='matern32',
                  normalised=True):
         super().__init__(model)
-        if kernel == 'sqexp':
-            raise ValueError("kernel 'sqexp' has no finite state: no filter "
-                             'evaluates it; GaussianProcessLikelihood does, '
-                             'up to %d data points' % N_GP_MAX)
-        if kernel not in GPS_KERNELS:
-            raise ValueError('kernel must be one of %s, not %r' %
-                             (', '.join(map(repr, GPS_KERNELS)), kernel))
+        terms = (kernel,) if isinstance(kernel, str) or \
+            not isinstance(kernel, (tuple, list)) else tuple(kernel)
+        for name in terms:
+            if isinstance(name, str) and name == 'sqexp':
+                raise ValueError("kernel 'sqexp' has no finite state: no "
+                                 'filter evaluates it; '
+                                 'GaussianProcessLikelihood does, up to %d '
+                                 'data points' % N_GP_MAX)
+            if not isinstance(name, str) or name not in GPS_KERNELS:
+                raise ValueError('kernel must be one of %s, not %r' %
+                                 (', '.join(map(repr, GPS_KERNELS)), name))
+        if isinstance(kernel, (tuple, list)):
+            if len(terms) == 1:
+                raise ValueError('a sequence of one kernel name is not a sum: '
+                                 'write kernel=%r, the string, for one term' %
+                                 terms[0])
+            states = sum(GPS_STATES[name] for name in terms)
+            if not 2 <= len(terms) <= GPS_MAX_TERMS or \
+                    states > GPS_MAX_STATES:
+                raise ValueError(
+                    'a sum of kernels has at most %d terms and at most %d '
+                    'states (exp 1, matern32 2, matern52 3, sho 2), not %d '
+                    'terms with %d states' % (GPS_MAX_TERMS, GPS_MAX_STATES,
+                                              len(terms), states))
+            kernel = terms
+            # the slots of nb_gps_terms.hip: the terms sorted by kernel code,
+            # equal names in their order, each with the column of its a
+            first = np.cumsum([0] + [3 if name == 'sho' else 2
+                                     for name in terms])
+            order = sorted(range(len(terms)),
+                           key=lambda i: GPS_KERNELS.index(terms[i]))
+            self._slots = tuple((terms[i], int(first[i])) for i in order)
         self.kernel = kernel
         data = _bounded_vector(data, 'data', N_GPS_MAX, 'data points')
         if not np.all(np.isfinite(data)):
@@ -1080,6 +1129,8 @@ class GaussianProcessSeriesLikelihood(_ModelLikelihood):
 
     @property
     def _width(self):
+        if isinstance(self.kernel, tuple):
+            return sum(3 if name == 'sho' else 2 for name in self.kernel) + 1
         return 4 if self.kernel == 'sho' else 3
 
     def _make_table(self):
@@ -1098,25 +1149,27 @@ class GaussianProcessSeriesLikelihood(_ModelLikelihood):
 
     def from_model(self, m, h):
         """log L of the rows of an (n, P) float64 model output and its (n, 3)
-        or (n, 4) hyper-parameters: cuda tensors in, a cuda tensor out; numpy
-        in, numpy out."""
+        or (n, 4) hyper-parameters ((n, W) for a sum of terms): cuda tensors
+        in, a cuda tensor out; numpy in, numpy out."""
         if isinstance(m, torch.Tensor) != isinstance(h, torch.Tensor):
             raise ValueError('the model output and the hyper-parameters must '
                              'both be torch tensors or both numpy arrays')
         return self._from_outputs(m, h)
 
-    def _transition(self, r, w, eta, inv_eta):
-        """Phi at the capped r = dt / l of every row, as ``gps_phi`` of
-        nb_gps.hip builds it: a list of rows of (n,) arrays."""
+    def _transition(self, r, w, eta, inv_eta, kernel=None):
+        """Phi of ``kernel`` (None: this likelihood's one kernel) at the
+        capped r = dt / l of every row, as ``gps_phi`` of nb_gps_stage.h
+        builds it: a list of rows of (n,) arrays."""
         ty = r.dtype.type
-        if self.kernel == 'exp':
+        kernel = self.kernel if kernel is None else kernel
+        if kernel == 'exp':
             return [[np.exp(-r)]]
-        if self.kernel == 'matern32':
+        if kernel == 'matern32':
             x = np.sqrt(ty(3)) * r
             e = np.exp(-x)
             ex = e * x
             return [[e * (1 + x), ex], [-ex, e * (1 - x)]]
-        if self.kernel == 'matern52':
+        if kernel == 'matern52':
             x = np.sqrt(ty(5)) * r
             e = np.exp(-x)
             x2 = x * x
@@ -1142,6 +1195,8 @@ class GaussianProcessSeriesLikelihood(_ModelLikelihood):
         m, h = np.asarray(m, float), np.asarray(h, float)
         self._check(m, h)
         ty = np.dtype(dtype).type
+        if isinstance(self.kernel, tuple):
+            return self._numpy_terms(m, h, ty)
         n, p = m.shape
         a, l, s = (h[:, i].astype(ty) for i in range(3))
         with np.errstate(all='ignore'):
@@ -1195,6 +1250,94 @@ class GaussianProcessSeriesLikelihood(_ModelLikelihood):
             out = ty(self.log_norm) - ty(0.5) * (q_sum + l_sum)
         out = np.where(bad, ty(np.nan), out)
         return out
+
+    def _numpy_terms(self, m, h, ty):
+        """The recursion of nb_gps_terms.hip for a sum of terms, with its
+        operations in its order: the slots' blocks of the state one after the
+        other, every sum over slots in slot order."""
+        n, p = m.shape
+        slots = self._slots
+        sizes = [GPS_STATES[name] for name, _ in slots]
+        offs = [sum(sizes[:i]) for i in range(len(slots))]
+        rs = range(sum(sizes))
+        with np.errstate(all='ignore'):
+            s = h[:, -1].astype(ty)
+            bad = ~((s >= 0) & (s < np.inf))
+            rows = []                            # a, 1 / l, w, eta, 1 / eta
+            for name, col in slots:
+                a, l = h[:, col].astype(ty), h[:, col + 1].astype(ty)
+                bad |= ~((a >= 0) & (a < np.inf)) | ~((l > 0) & (l < np.inf))
+                inv_l = np.minimum(1 / l, ty(np.finfo(np.float64).max))
+                w = eta = inv_eta = None
+                if name == 'sho':
+                    q = h[:, col + 2].astype(ty)
+                    bad |= ~((q > 0.5) & (q < np.inf))
+                    w = 1 / (2 * q)
+                    eta = np.sqrt(1 - w * w)
+                    inv_eta = 1 / eta
+                rows.append((a, inv_l, w, eta, inv_eta))
+            total = sum_in_order(row[0] for row in rows)
+            zero = np.zeros(n, ty)
+            big_g = [[zero for _ in rs] for _ in rs]
+            g = [zero for _ in rs]
+            q_sum, q_low, l_sum = zero, zero, zero
+            md = m.astype(ty)
+            for j in range(p):
+                phis = [self._transition(
+                    np.minimum(ty(self._dt[j]) * inv_l, ty(GPS_CAP)), w, eta,
+                    inv_eta, name)
+                    for (name, _), (_, inv_l, w, eta, inv_eta)
+                    in zip(slots, rows)]
+                # 1. the lower blocks, mirrored; then g
+                for bi, (oi, ri, phi_i) in enumerate(zip(offs, sizes, phis)):
+                    for bj in range(bi + 1):
+                        oj, rj, phi_j = offs[bj], sizes[bj], phis[bj]
+                        t = [[sum_in_order(phi_i[i][k] * big_g[oi + k][oj + c]
+                                           for k in range(ri))
+                              for c in range(rj)] for i in range(ri)]
+                        for i in range(ri):
+                            for c in range(i + 1 if bi == bj else rj):
+                                big_g[oi + i][oj + c] = \
+                                    big_g[oj + c][oi + i] = sum_in_order(
+                                        t[i][k] * phi_j[c][k]
+                                        for k in range(rj))
+                gn = [None for _ in rs]
+                for oi, ri, phi_i in zip(offs, sizes, phis):
+                    for i in range(ri):
+                        gn[oi + i] = sum_in_order(phi_i[i][k] * g[oi + k]
+                                                  for k in range(ri))
+                # 2. what the observation sees of G, and the pivot
+                gh = [sum_in_order(big_g[i][o] for o in offs) for i in rs]
+                c_sum = sum_in_order(gh[o] for o in offs)
+                g_sum = sum_in_order(gn[o] for o in offs)
+                noise = ty(self._sigma2[j]) + s
+                d = (total - c_sum) + noise
+                # 3.
+                v = (md[:, j] - ty(self.data[j])) - g_sum
+                bad |= ~np.isfinite(md[:, j]) | ~((d > 0) & (d < np.inf))
+                inv_d = 1 / d
+                # 4. u = a p - Gh, p = [1], [1, 0], [1, 0, -1/3], [1, 0]
+                u = [None for _ in rs]
+                for o, r, row in zip(offs, sizes, rows):
+                    u[o] = row[0] - gh[o]
+                    if r > 1:
+                        u[o + 1] = -gh[o + 1]
+                    if r > 2:
+                        u[o + 2] = row[0] * -(1 / ty(3)) - gh[o + 2]
+                k = [u[i] * inv_d for i in rs]
+                # 5.
+                g = [gn[i] + k[i] * v for i in rs]
+                for i in rs:
+                    for c in range(i + 1):
+                        big_g[i][c] = big_g[c][i] = big_g[i][c] + u[i] * k[c]
+                # 6.
+                y = (v * v) * inv_d - q_low          # a compensated sum
+                q_new = q_sum + y
+                q_low = (q_new - q_sum) - y
+                q_sum = q_new
+                l_sum = l_sum + np.log(d)
+            out = ty(self.log_norm) - ty(0.5) * (q_sum + l_sum)
+        return np.where(bad, ty(np.nan), out)
 
 
 class RosenbrockLikelihood:
