@@ -629,6 +629,46 @@ class PriorTable(_Table):
         return out
 
 
+MIXTURE_MAX_DIM = 128              # 16 NB_MAX_DT
+MIXTURE_MAX_COMPONENTS = 4096      # NB_MIXTURE_MAX_COMPONENTS
+MIXTURE_LDS_BYTES = 160 * 1024     # MX_LDS_BYTES of nb_mixture.hip
+
+
+def mixture_record(dt):
+    """Doubles of one component's record (nb_layout.h, ``nb_mixture_record``):
+    dt (dt + 1) / 2 tiles of 256, then mu [16 dt] and a_k rounded up to a
+    multiple of 128."""
+    return dt * (dt + 1) // 2 * 256 + (16 * dt + 1 + 127) // 128 * 128
+
+
+def mixture_launch_shape(n_dim, n_components):
+    """(dt, kl, small, tpw, resident, points_per_round) of
+    ``nb_mixture_loglike`` (nb_mixture.hip, ``launch`` / ``launch_variant``):
+    the kernel is instantiated for dt = ceil(n_dim / 16) tiles, ``kl`` k-steps
+    that hold real features and ``small`` (the last row tile has at most 4
+    real rows, n_dim mod 16 in 1..4); a wavefront owns ``tpw`` tiles of 16
+    points; ``resident`` tells whether all records fit the LDS of a CU (else
+    they stream through it).  ``points_per_round`` is what one trip of the
+    kernel's loop over points covers: the cap on workgroups (256, times the
+    workgroups a CU holds for the resident kernel) x 8 wavefronts x 16 tpw."""
+    if not 1 <= n_dim <= MIXTURE_MAX_DIM:
+        raise ValueError('n_dim must be 1..%d, not %d' %
+                         (MIXTURE_MAX_DIM, n_dim))
+    if not 1 <= n_components <= MIXTURE_MAX_COMPONENTS:
+        raise ValueError('n_components must be 1..%d, not %d' %
+                         (MIXTURE_MAX_COMPONENTS, n_components))
+    dt = (n_dim + 15) // 16
+    rem = n_dim % 16
+    full = 2 * ((n_dim + 7) // 8) == 4 * dt
+    kl = 4 * dt if full else 4 * dt - 2
+    small = not full and 1 <= rem <= 4
+    tpw = 4 if dt <= 2 else 2 if dt <= 4 else 1
+    lds = n_components * mixture_record(dt) * 8
+    resident = lds <= MIXTURE_LDS_BYTES
+    per_cu = 2 if resident and MIXTURE_LDS_BYTES // lds >= 2 else 1
+    return dt, kl, small, tpw, resident, 256 * per_cu * 8 * 16 * tpw
+
+
 class MixtureTable(_Table):
     """Device-resident components of a Gaussian mixture
     (``nb_mixture_create``): means (K, D), the lower-triangular inverse

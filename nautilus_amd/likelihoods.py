@@ -191,7 +191,13 @@ class GaussianMixtureLikelihood(_DeviceTables):
     point once, for unequal weights and correlated components.  With
     ``labels=True`` a call returns ``(log_l, label)``, ``label`` being the
     int32 index of the largest term (the component a point belongs to);
-    ``Sampler`` carries it through as a blob."""
+    ``Sampler`` carries it through as a blob.
+
+    A non-finite entry in row i of the points makes ``log_l[i]`` of the fused
+    kernel NaN -- or -inf, where an infinite entry meets no exact zero of any
+    inverse Cholesky factor or of its padding -- never a finite value or +inf,
+    and changes no bit of the value or the label of any other row; the label
+    of such a row means nothing."""
 
     device = True
 

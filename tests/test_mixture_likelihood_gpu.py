@@ -1,71 +1,19 @@
 """The fused device likelihood of weighted, full-covariance Gaussian mixtures
 (``nb_mixture_loglike``, nautilus_amd/csrc/nb_mixture.hip) against its numpy
-twin and scipy, and end to end through ``Sampler``."""
+twin and scipy, and end to end through ``Sampler``.  (Problems and points
+come from mixture_cases.py; every instantiation of the kernel is swept in
+test_mixture_sweep_gpu.py.)"""
 
 import numpy as np
 import pytest
 
+from mixture_cases import (ATOL, RTOL, overlapping, points, problem,
+                           scipy_terms)
+
 pytestmark = pytest.mark.gpu
 
-RTOL, ATOL = 1e-11, 1e-8          # the band tests/test_hip_parity.py holds the
-#                                   mixture of config 4 to
 GRID = [(1, 2), (2, 1), (3, 5), (17, 3), (49, 3), (50, 4), (50, 64), (100, 7),
         (127, 2), (128, 16)]
-# z_k ~ OVERLAP_SCALE * N(0, I / D): the distance between two means is about
-# sqrt(2) OVERLAP_SCALE standard deviations, so the terms of two components
-# differ by about OVERLAP_SCALE^2 +- sqrt(2) OVERLAP_SCALE nats at a draw
-OVERLAP_SCALE = 1.0
-
-
-def _random_cov(d, rng, cond=1e3):
-    q, _ = np.linalg.qr(rng.normal(size=(d, d)))
-    ev = (0.01 + 0.03 * rng.random())**2 * np.logspace(0, -np.log10(cond), d)
-    rng.shuffle(ev)
-    return (q * ev) @ q.T
-
-
-def problem(d, k, seed, cond=1e3):
-    """Well separated components with covariances of their own."""
-    rng = np.random.default_rng(seed)
-    means = 0.25 + 0.5 * rng.random((k, d))
-    covs = np.stack([_random_cov(d, rng, cond) for _ in range(k)])
-    w = rng.random(k) + 0.05
-    return means, covs, w / w.sum()
-
-
-def overlapping(d, k, seed, cond=1e3):
-    """One shared covariance L L^T, means mu_0 + L z_k a standard deviation
-    or so apart: every point has several terms of similar size."""
-    rng = np.random.default_rng(seed)
-    cov = _random_cov(d, rng, cond)
-    chol = np.linalg.cholesky(cov)
-    z = OVERLAP_SCALE * rng.normal(size=(k, d)) / np.sqrt(d)
-    means = 0.5 + z @ chol.T
-    w = rng.random(k) + 0.05
-    return means, cov, w / w.sum()
-
-
-def draws(means, covs, w, n, rng):
-    covs = np.broadcast_to(covs, (len(means),) + covs.shape[-2:])
-    which = rng.choice(len(means), size=n, p=w)
-    chol = np.linalg.cholesky(covs)
-    eps = rng.normal(size=(n, means.shape[1]))
-    return means[which] + np.einsum('nij,nj->ni', chol[which], eps)
-
-
-def points(means, covs, w, seed):
-    """2000 draws from the mixture and 2000 uniform points of the cube (the
-    far tails: log L down to about -1e6)."""
-    rng = np.random.default_rng(seed + 1000)
-    return np.vstack([draws(means, covs, w, 2000, rng),
-                      rng.random((2000, means.shape[1]))])
-
-
-def scipy_terms(means, covs, w, x):
-    from scipy.stats import multivariate_normal
-    covs = np.broadcast_to(covs, (len(means),) + covs.shape[-2:])
-    return np.array([np.log(w[i]) + np.atleast_1d(multivariate_normal(
-        means[i], covs[i]).logpdf(x)) for i in range(len(means))])
 
 
 def _cases():
