@@ -25,8 +25,19 @@ namespace {
 // the last row up (row r only needs z_0..z_r), and the 64 x D block is then
 // written with fully coalesced stores.  Splitting a proposal over wavefronts
 // instead of giving each wavefront its own 64 proposals keeps the LDS
-// footprint per wavefront at a quarter: 24 wavefronts per CU instead of 6
-// hide the latency of the dependent fp64 chains.
+// footprint per wavefront at a quarter; the kernel is chains of dependent
+// fp64 operations, and the wavefronts resident on a SIMD are what hides their
+// latency.  A workgroup puts one wavefront on each SIMD, so wavefronts per
+// SIMD = workgroups per CU = min(registers, LDS), as compiled for gfx950
+// (-O3, compiler resource remarks; no instantiation uses scratch):
+//   DT (n_dim)     1 (<=16) 2 (<=32) 3 (<=48) 4 (<=64) 5 (<=80) 6 (<=96) 7 (<=112) 8 (<=128)
+//   VGPRs             68       68       70       70       78       86       94       102
+//   by registers       7        7        7        7        6        5        5         4
+//   (whole z in registers, before:  68/7  74/6  107/4  139/3  171/2  203/2  235/2  256/1)
+//   by LDS, floor(160 KiB / (520 n_dim + 2816 B)), at most 8:
+//     n_dim <= 33: 8   <= 39: 7   <= 47: 6   <= 57: 5   <= 73: 4   <= 99: 3   else 2
+// so n_dim 50 runs five wavefronts per SIMD (three before), 64 four (three),
+// and from n_dim 58 on LDS, not the registers, sets the number (100: two).
 // ---------------------------------------------------------------------------
 constexpr int ZS = 65;     // LDS row stride (odd: transposed reads conflict-free)
 constexpr int DW = 4;      // wavefronts per workgroup
@@ -56,6 +67,75 @@ __device__ __forceinline__ double draw_row(const double* __restrict__ B,
   return acc;
 }
 
+// x = B z + c in place for a single-member bound: wavefront `wave` computes
+// the rows r = 4 i + wave, i < 4 DT, of its 64 proposals.  z passes through
+// registers ZB slots at a time; each block advances the accumulators of every
+// row that reaches into it, so a slot is read from LDS once per wavefront and
+// the registers hold ZB slots + 4 DT accumulators, not the whole z.  Per row
+// the sum is the one of draw_row's order: j ascending from 0, one fused
+// multiply-add per term, and the up to three terms between the diagonal and
+// the next multiple of four keep their zero weight (B is padded; slots >= ne
+// read as 0).  Rows are advanced RG (one or two) at a time under one
+// wave-uniform test of the first: the chains of a group are independent and
+// interleave.  A row >= ne of a group whose first row is < ne is computed and
+// dropped; its B reads stay inside the member's block, whose B has 16 DT full
+// rows.
+// Blocks that start at or beyond ne feed no row < ne and are skipped.
+constexpr int ZB = 16;     // z slots in registers at a time
+
+template <int DT>
+__device__ __forceinline__ void draw_product_single(
+    const double* __restrict__ Bp, const double* __restrict__ c, double* zs,
+    int ne, int wave, int lane) {
+  constexpr int NR = 4 * DT;            // rows per wavefront
+  // rows advanced together: two from DT 5 on, where LDS leaves a SIMD two to
+  // four wavefronts, one below, where four or more are resident -- measured
+  // both ways at n_dim 50, 64 and 100 (profiles/draw_blocks/variants.txt)
+  constexpr int RG = DT >= 5 ? 2 : 1;
+  static_assert(16 % ZB == 0 && ZB % (4 * RG) == 0 && NR % RG == 0,
+                "blocks tile the 16 DT slots, row groups tile a block");
+  double acc[NR];
+#pragma unroll
+  for (int i = 0; i < NR; ++i) acc[i] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 16 * DT / ZB; ++k) {
+    if (k * ZB < ne) {
+      double z[ZB];
+#pragma unroll
+      for (int u = 0; u < ZB; ++u)
+        z[u] = (k * ZB + u < ne) ? zs[(k * ZB + u) * ZS + lane] : 0.0;
+#pragma unroll
+      for (int i0 = k * ZB / 4; i0 < NR; i0 += RG) {
+        if (4 * i0 + wave < ne) {
+          const double* brow[RG];
+#pragma unroll
+          for (int g = 0; g < RG; ++g) {
+            const int r = 4 * (i0 + g) + wave;
+            brow[g] = Bp + r * (r + 1) / 2;
+          }
+#pragma unroll
+          for (int u = 0; u < ZB; ++u) {
+            const int j = k * ZB + u;
+#pragma unroll
+            for (int g = 0; g < RG; ++g) {
+              if (j < 4 * (i0 + g) + 4) {          // compile time
+                const double b = brow[g][j];
+                acc[i0 + g] += ((j <= 4 * (i0 + g) + wave) ? b : 0.0) * z[u];
+              }
+            }
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();                      // all of z is read before it is replaced
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    const int r = 4 * i + wave;
+    if (r < ne) zs[r * ZS + lane] = acc[i] + c[r];
+  }
+}
+
 template <int DT>
 __global__ void __launch_bounds__(64 * DW)
 nb_draw_kernel(const double* __restrict__ blob, unsigned long long seed,
@@ -63,7 +143,12 @@ nb_draw_kernel(const double* __restrict__ blob, unsigned long long seed,
                double* __restrict__ x_out) {
   extern __shared__ __attribute__((aligned(16))) double zs[];   // [slot][ZS]
   __shared__ int member_of[64];
-  __shared__ double norm_part[DW][64];
+  // the norm partials are dead after the rescale; a single-member bound then
+  // keeps its slot table (column -> slot) in their place
+  __shared__ union {
+    double norm_part[DW][64];
+    int slot_of[128];
+  } sh;
   __shared__ double radius_of[64];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -125,7 +210,7 @@ nb_draw_kernel(const double* __restrict__ blob, unsigned long long seed,
       }
     }
   }
-  norm_part[wave][lane] = part;
+  sh.norm_part[wave][lane] = part;
   // cube part: slots ne..ne+nc-1 (basic.py:85, 633-640)
   for (int j = wave; 2 * j < nc; j += DW) {
     double u0, u1;
@@ -136,9 +221,9 @@ nb_draw_kernel(const double* __restrict__ blob, unsigned long long seed,
   __syncthreads();
 
   // |z| -> u^(1/D): every wavefront rescales the slots it wrote
-  double norm2 = norm_part[0][lane];
+  double norm2 = sh.norm_part[0][lane];
 #pragma unroll
-  for (int w = 1; w < DW; ++w) norm2 += norm_part[w][lane];
+  for (int w = 1; w < DW; ++w) norm2 += sh.norm_part[w][lane];
   const double scale = radius_of[lane] / sqrt(norm2);
   for (int j = wave; 2 * j < ne; j += DW) {
     zs[(2 * j) * ZS + lane] *= scale;
@@ -147,30 +232,13 @@ nb_draw_kernel(const double* __restrict__ blob, unsigned long long seed,
   __syncthreads();
 
   if (K == 1) {
-    // One member: B is wave uniform.  Every wavefront takes the whole z of
-    // its 64 proposals into registers (one LDS read per slot instead of one
-    // per term of every row) and computes the rows r = 4 i + wave with scalar
-    // B operands; same accumulation order as draw_row (j ascending, the up to
-    // three terms beyond the diagonal carry a zero weight; B is padded).
-    double z[16 * DT];
-#pragma unroll
-    for (int j = 0; j < 16 * DT; ++j) z[j] = (j < ne) ? zs[j * ZS + lane] : 0.0;
-    __syncthreads();                    // all of z is read before it is replaced
-    const double* Bp = draw + 2 + 4 * dp;
-#pragma unroll
-    for (int i = 0; i < 4 * DT; ++i) {
-      const int r = 4 * i + wave;
-      if (r < ne) {
-        const double* brow = Bp + (long long)r * (r + 1) / 2;
-        double acc = 0.0;
-#pragma unroll
-        for (int j = 0; j < 4 * i + 4; ++j) {
-          const double b = brow[j];
-          acc += ((j <= r) ? b : 0.0) * z[j];
-        }
-        zs[r * ZS + lane] = acc + c[r];
-      }
-    }
+    // One member: B is wave uniform, so the B operands are scalar loads and
+    // every wavefront reads each z slot of its 64 proposals from LDS once
+    // (not once per term of every row).
+    if ((int)threadIdx.x < n_dim)
+      sh.slot_of[threadIdx.x] =
+          (int)((const long long*)(draw + 2 + 2 * dp))[threadIdx.x];
+    draw_product_single<DT>(draw + 2 + 4 * dp, c, zs, ne, wave, lane);
     __syncthreads();
   } else {
   // x = B z + c in place, four rows per step from the last row up; the rows
@@ -207,6 +275,15 @@ nb_draw_kernel(const double* __restrict__ blob, unsigned long long seed,
   int row = (int)threadIdx.x / n_dim, col = (int)threadIdx.x - row * n_dim;
   const int drow = nt / n_dim, dcol = nt - drow * n_dim;
   double* dst = x_out + i0 * n_dim;
+  if (K == 1) {
+    // one member: its slot table was staged in LDS once per workgroup
+    for (int e = threadIdx.x; e < total; e += nt) {
+      dst[e] = zs[sh.slot_of[col] * ZS + row];
+      row += drow; col += dcol;
+      if (col >= n_dim) { col -= n_dim; ++row; }
+    }
+    return;
+  }
   for (int e = threadIdx.x; e < total; e += nt) {
     const long long* sl = (const long long*)(draw + member_of[row] *
                                              draw_stride) + 2 + 2 * dp;
