@@ -713,7 +713,7 @@ int nb_gp_destroy(nb_gp* h);
  *                    eta = sqrt(1 - 1 / (4 q^2)): the underdamped oscillator
  *                    of frequency 1 / l
  * the covariances of linear stochastic differential equations with 1, 2, 3
- * and 2 states; the recursion is written out in nb_gps.hip.  For the first
+ * and 2 states; the recursion is written out in nb_gps_filter.h.  For the first
  * three K is that of nb_gp_loglike with the same kernel.  A gap t_j - t_j-1
  * enters as min((t_j - t_j-1) / l, 1e4), beyond which the exponentials of the
  * first three kernels are 0 in float64 (for NB_GPS_SHO that holds up to q of
@@ -789,12 +789,12 @@ int nb_gps_destroy(nb_gps* h);
  *   5. g <- g + k v; G <- G + u k^T on the lower triangle, mirrored
  *   6. Q += v^2 / d as a compensated sum; log d through the product of the
  *      mantissas and the sum of the exponents, renormalised every 256 steps
- * and out_dev[i] = log_norm - (Q + L) / 2 (nb_gps_terms.hip).  A row is NaN,
+ * and out_dev[i] = log_norm - (Q + L) / 2 (nb_gps_filter.h).  A row is NaN,
  * and changes no other row, with an m_ij that is not finite; any a_I negative
  * or not finite (a_I = 0 is legal and switches the term off); any l_I outside
  * (0, +inf); any q_I outside (1/2, +inf); an s negative or not finite; or a
  * pivot outside (0, +inf).  One difference from a single term: the form G00 =
- * a - noise k0 that nb_gps.hip uses has no exact analogue for a sum, so a
+ * a - noise k0 that one term uses has no exact analogue for a sum, so a
  * repeated time with sigma2_j + s = 0 is unspecified here: that row is NaN or
  * finite, other rows are untouched, and nothing worse happens.             */
 #define NB_GPS_MAX_TERMS 3

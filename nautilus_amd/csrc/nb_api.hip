@@ -904,15 +904,13 @@ int nb_gp_loglike(const nb_gp* h, int32_t mode, const double* model,
                       ld_cov, n, h->log_norm, out, as_stream(stream));
 }
 
-// Steps, data and sigma^2 for nb_gps.hip (nb_layout.h, NB_GPS_STRIDE),
-// uploaded once.
+// Steps, data and sigma^2 for nb_gps_filter.h (nb_layout.h, NB_GPS_STRIDE),
+// uploaded once, and where a hyper row holds the terms.
 struct nb_gps {
   double* dev = nullptr;
   int n_data = 0;
-  int kernel = 0;
   double log_norm = 0.0;
-  int width = 0;                                 // doubles of a hyper row
-  nb_gps_plan plan;                              // n_terms 0: one term
+  nb_gps_plan plan;
 };
 
 int nb_gps_create(int32_t n_data, const double* t, const double* data,
@@ -923,9 +921,8 @@ int nb_gps_create(int32_t n_data, const double* t, const double* data,
                           &image);
   nb_gps h;
   h.n_data = n_data;
-  h.kernel = kernel;
   h.log_norm = log_norm;
-  h.width = kernel == NB_GPS_SHO ? 4 : 3;
+  h.plan = plan_gps_one(kernel);
   return nb_make_table(rc, image, "Gaussian-process series likelihood", h,
                        out);
 }
@@ -941,9 +938,7 @@ int nb_gps_create_terms(int32_t n_data, const double* t, const double* data,
   rc = pack_gps(n_data, t, data, sigma2, h.plan.kind[0], log_norm, out,
                 &image);
   h.n_data = n_data;
-  h.kernel = h.plan.kind[0];
   h.log_norm = log_norm;
-  h.width = h.plan.width;
   return nb_make_table(rc, image, "Gaussian-process series likelihood", h,
                        out);
 }
@@ -958,7 +953,7 @@ int nb_gps_loglike(const nb_gps* h, const double* model, int64_t ld,
                  "handle, n >= 0)");
     return NB_ERR_ARG;
   }
-  const int64_t width = h->width;
+  const int64_t width = h->plan.width;
   if ((n > 1 && (ld < h->n_data || ld_hyper < width)) ||
       (n > 0 && (model == nullptr || hyper == nullptr || out == nullptr))) {
     nb_set_error("bad Gaussian-process series likelihood arguments (ld >= "
@@ -966,12 +961,7 @@ int nb_gps_loglike(const nb_gps* h, const double* model, int64_t ld,
                  (long long)width);
     return NB_ERR_ARG;
   }
-  if (h->plan.n_terms > 1)
-    return nb_launch_gps_terms(h->dev, h->n_data, h->plan.n_terms,
-                               h->plan.kind, h->plan.col, h->plan.col_s,
-                               model, ld, hyper, ld_hyper, n, h->log_norm,
-                               out, as_stream(stream));
-  return nb_launch_gps(h->dev, h->n_data, h->kernel, model, ld, hyper,
+  return nb_launch_gps(h->dev, h->n_data, h->plan, model, ld, hyper,
                        ld_hyper, n, h->log_norm, out, as_stream(stream));
 }
 

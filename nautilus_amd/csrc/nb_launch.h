@@ -73,15 +73,10 @@ int nb_launch_gp(const double* tab, int n_data, int kernel, int mode,
                  const double* model, long long ld, const double* cov,
                  long long ld_cov, long long n, double log_norm, double* out,
                  hipStream_t stream);
-int nb_launch_gps(const double* tab, int n_data, int kernel,
+int nb_launch_gps(const double* tab, int n_data, const nb_gps_plan& plan,
                   const double* model, long long ld, const double* hyper,
                   long long ld_hyper, long long n, double log_norm,
                   double* out, hipStream_t stream);
-int nb_launch_gps_terms(const double* tab, int n_data, int n_terms,
-                        const int* kinds, const int* cols, int col_s,
-                        const double* model, long long ld,
-                        const double* hyper, long long ld_hyper, long long n,
-                        double log_norm, double* out, hipStream_t stream);
 int nb_launch_fold_poisson(const double* blob, int n_data, int n_src,
                            const double* src, long long ld, long long n,
                            double log_const, double* out, hipStream_t stream);

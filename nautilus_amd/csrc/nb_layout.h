@@ -168,10 +168,10 @@ constexpr int nb_gp_lds_doubles(int t) {
 // wavefronts of a workgroup at T tiles
 constexpr int nb_gp_waves(int t) { return t <= 2 ? 1 : t <= 4 ? 2 : 4; }
 
-// Gaussian-process likelihood of an ordered series (nb_gps.hip).  The table is
-// NB_GPS_STRIDE doubles per datum j: dt_j = t_j - t_j-1 rounded once (dt_0 =
-// 0), d_j, sigma_j^2 and a zero -- 32 aligned bytes, one scalar load of the
-// wavefront per step.  The kernel stages the model's rows through LDS in
+// Gaussian-process likelihood of an ordered series (nb_gps_filter.h).  The
+// table is NB_GPS_STRIDE doubles per datum j: dt_j = t_j - t_j-1 rounded once
+// (dt_0 = 0), d_j, sigma_j^2 and a zero -- 32 aligned bytes, one scalar load of
+// the wavefront per step.  The kernel stages the model's rows through LDS in
 // blocks of NB_GPS_BLOCK columns.
 #define NB_GPS_STRIDE 4
 #define NB_GPS_DT 0
@@ -181,6 +181,23 @@ constexpr int nb_gp_waves(int t) { return t <= 2 ? 1 : t <= 4 ? 2 : 4; }
 constexpr size_t nb_gps_table_doubles(int p) {
   return (size_t)NB_GPS_STRIDE * (size_t)p;
 }
+
+// Where the kernel finds the one to three terms in a row of the hyper input
+// (plan_gps_one, plan_gps_terms of nb_pack.h): the slots are the terms sorted
+// by kernel code, equal codes in the caller's order; kind[I] is the code of
+// slot I, col[I] the column of its (a, l) and, for NB_GPS_SHO, col_q[I] that
+// of its q (0 otherwise: not read); col_s is the column of s.  One term's row
+// is (a, l, s[, q]); a sum's holds (a, l[, q]) per term in the CALLER's order
+// and s in its last column, col_s = width - 1.
+struct nb_gps_plan {
+  int n_terms = 0;
+  int kind[3] = {0, 0, 0};                       // NB_GPS_MAX_TERMS
+  int col[3] = {0, 0, 0};
+  int col_q[3] = {0, 0, 0};
+  int col_s = 0;
+  int width = 0;                                 // doubles of a hyper row
+  int states = 0;
+};
 
 // Prior table (nb_transform.hip, PT_* rows): one allocation holding
 // par[NB_PRIOR_NPAR][n_dim], key_value[n_keys], key_column[n_keys] (int) and

@@ -848,7 +848,7 @@ int pack_gp(int32_t n_data, const double* data, const double* sigma2,
   return NB_OK;
 }
 
-// The steps t_j - t_j-1, data and sigma^2 for nb_gps.hip (nb_layout.h,
+// The steps t_j - t_j-1, data and sigma^2 for nb_gps_filter.h (nb_layout.h,
 // NB_GPS_STRIDE doubles per datum)
 int pack_gps(int32_t n_data, const double* t, const double* data,
              const double* sigma2, int32_t kernel, double log_norm,
@@ -898,19 +898,24 @@ int pack_gps(int32_t n_data, const double* t, const double* data,
   return NB_OK;
 }
 
-// Where nb_gps_terms.hip finds the terms of a sum: the slots are the terms
-// sorted by kernel code, equal codes in the caller's order; kind[I] is the
-// code of slot I, col[I] the column of its (a, l[, q]) in a row of the hyper
-// input, which holds the terms in the CALLER's order and s in its last column
-// col_s = width - 1.
-struct nb_gps_plan {
-  int n_terms = 0;
-  int kind[NB_GPS_MAX_TERMS] = {0, 0, 0};
-  int col[NB_GPS_MAX_TERMS] = {0, 0, 0};
-  int col_s = 0;
-  int width = 0;
-  int states = 0;
-};
+static_assert(NB_GPS_MAX_TERMS == 3, "the slots of nb_gps_plan (nb_layout.h)");
+
+constexpr int gps_plan_states(int kernel) {
+  return kernel == NB_GPS_EXP ? 1 : kernel == NB_GPS_MATERN52 ? 3 : 2;
+}
+
+// The plan of one term, whose hyper row is (a, l, s[, q]); pack_gps checks
+// the kernel.
+nb_gps_plan plan_gps_one(int32_t kernel) {
+  nb_gps_plan p;
+  p.n_terms = 1;
+  p.kind[0] = kernel;
+  p.col_q[0] = kernel == NB_GPS_SHO ? 3 : 0;
+  p.col_s = 2;
+  p.width = kernel == NB_GPS_SHO ? 4 : 3;
+  p.states = gps_plan_states(kernel);
+  return p;
+}
 
 // The checks of nb_gps_create_terms that nb_gps_create does not have, and
 // the plan; pack_gps checks the rest and packs the same image.
@@ -941,8 +946,7 @@ int plan_gps_terms(int32_t n_terms, const int32_t* kernels, const double* t,
     }
     first[i] = column;
     column += kernels[i] == NB_GPS_SHO ? 3 : 2;
-    p.states += kernels[i] == NB_GPS_EXP ? 1
-                : kernels[i] == NB_GPS_MATERN52 ? 3 : 2;
+    p.states += gps_plan_states(kernels[i]);
   }
   if (p.states > NB_GPS_MAX_STATES) {
     nb_set_error("the terms of the Gaussian-process series likelihood have %d "
@@ -964,6 +968,7 @@ int plan_gps_terms(int32_t n_terms, const int32_t* kernels, const double* t,
   for (int i = 0; i < n_terms; ++i) {
     p.kind[i] = kernels[order[i]];
     p.col[i] = first[order[i]];
+    p.col_q[i] = p.kind[i] == NB_GPS_SHO ? p.col[i] + 2 : 0;
   }
   *plan = p;
   return NB_OK;

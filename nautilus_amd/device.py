@@ -891,7 +891,7 @@ GP = GPTable
 GPS_KERNELS = {'exp': 0, 'matern32': 1, 'matern52': 2, 'sho': 3}  # NB_GPS_*
 GPS_MAX_DATA = 1 << 20             # NB_GPS_MAX_DATA
 GPS_BLOCK = 32                     # NB_GPS_BLOCK of nb_layout.h: the columns
-#                                    of a block nb_gps.hip stages through LDS
+#                                    of a block nb_gps_filter.h stages through LDS
 
 
 def gps_width(kernel):

@@ -1055,7 +1055,7 @@ class GaussianProcessSeriesLikelihood(_ModelLikelihood):
     (a_i, l_i) or for 'sho' (a_i, l_i, q_i), and s in one last column: W =
     sum w_i + 1 <= 10.  The sum is itself a state-space kernel -- the states
     concatenated, the transition block diagonal -- and the same kind of
-    filter walks it with a state of at most 6 x 6 numbers (nb_gps_terms.hip,
+    filter walks it with a state of at most 6 x 6 numbers (nb_gps_filter.h,
     whose header states the recursion).  Inside, the terms are sorted by
     kernel, equal names in their order: naming them in another order together
     with their columns changes no bit.  The NaN rules hold for every a_i (a_i
@@ -1096,7 +1096,7 @@ class GaussianProcessSeriesLikelihood(_ModelLikelihood):
                     'terms with %d states' % (GPS_MAX_TERMS, GPS_MAX_STATES,
                                               len(terms), states))
             kernel = terms
-            # the slots of nb_gps_terms.hip: the terms sorted by kernel code,
+            # the slots of nb_gps_filter.h: the terms sorted by kernel code,
             # equal names in their order, each with the column of its a
             first = np.cumsum([0] + [3 if name == 'sho' else 2
                                      for name in terms])
@@ -1135,9 +1135,7 @@ class GaussianProcessSeriesLikelihood(_ModelLikelihood):
 
     @property
     def _width(self):
-        if isinstance(self.kernel, tuple):
-            return sum(3 if name == 'sho' else 2 for name in self.kernel) + 1
-        return 4 if self.kernel == 'sho' else 3
+        return device.gps_width(self.kernel)
 
     def _make_table(self):
         return device.GPSTable(self.t, self.data, self._sigma2,
@@ -1162,12 +1160,12 @@ class GaussianProcessSeriesLikelihood(_ModelLikelihood):
                              'both be torch tensors or both numpy arrays')
         return self._from_outputs(m, h)
 
-    def _transition(self, r, w, eta, inv_eta, kernel=None):
-        """Phi of ``kernel`` (None: this likelihood's one kernel) at the
-        capped r = dt / l of every row, as ``gps_phi`` of nb_gps_stage.h
-        builds it: a list of rows of (n,) arrays."""
+    @staticmethod
+    def _transition(kernel, r, w, eta, inv_eta):
+        """Phi of ``kernel`` at the capped r = dt / l of every row, as
+        ``gps_phi`` of nb_gps_filter.h builds it: a list of rows of (n,)
+        arrays."""
         ty = r.dtype.type
-        kernel = self.kernel if kernel is None else kernel
         if kernel == 'exp':
             return [[np.exp(-r)]]
         if kernel == 'matern32':
@@ -1195,88 +1193,35 @@ class GaussianProcessSeriesLikelihood(_ModelLikelihood):
     def numpy_from_model(self, m, h, dtype=np.float64):
         """Pure-numpy evaluation of an (n, P) model output and its
         hyper-parameters (CPU baseline / oracle runs / tests): the recursion
-        of nb_gps.hip with its operations in its order, vectorised over the
-        rows, in ``dtype`` -- ``np.longdouble`` gives the tests their truth.
-        Every ``dtype`` starts from the same float64 inputs."""
+        that nb_gps_filter.h states, with its operations in its order -- the
+        slots' blocks of the state one after the other, every sum over slots
+        in slot order -- vectorised over the rows, in ``dtype``:
+        ``np.longdouble`` gives the tests their truth.  Every ``dtype`` starts
+        from the same float64 inputs."""
         m, h = np.asarray(m, float), np.asarray(h, float)
         self._check(m, h)
         ty = np.dtype(dtype).type
+        n, p = m.shape
+        # (name, column of a, column of q) of every slot, and the column of s
         if isinstance(self.kernel, tuple):
-            return self._numpy_terms(m, h, ty)
-        n, p = m.shape
-        a, l, s = (h[:, i].astype(ty) for i in range(3))
-        with np.errstate(all='ignore'):
-            bad = ~((a >= 0) & (a < np.inf)) | ~((l > 0) & (l < np.inf)) | \
-                ~((s >= 0) & (s < np.inf))
-            inv_l = np.minimum(1 / l, ty(np.finfo(np.float64).max))
-            w = eta = inv_eta = None
-            states = {'exp': 1, 'matern32': 2, 'matern52': 3, 'sho': 2}[
-                self.kernel]
-            if self.kernel == 'sho':
-                q = h[:, 3].astype(ty)
-                bad |= ~((q > 0.5) & (q < np.inf))
-                w = 1 / (2 * q)
-                eta = np.sqrt(1 - w * w)
-                inv_eta = 1 / eta
-            rr = range(states)
-            zero = np.zeros(n, ty)
-            big_g = [[zero for _ in rr] for _ in rr]
-            g = [zero for _ in rr]
-            q_sum, q_low, l_sum = zero, zero, zero
-            md = m.astype(ty)
-            for j in range(p):
-                r = np.minimum(ty(self._dt[j]) * inv_l, ty(GPS_CAP))
-                phi = self._transition(r, w, eta, inv_eta)
-                t = [[sum_in_order(phi[i][k] * big_g[k][c] for k in rr)
-                      for c in rr] for i in rr]
-                for i in rr:
-                    for c in range(i + 1):
-                        big_g[i][c] = big_g[c][i] = sum_in_order(
-                            t[i][k] * phi[c][k] for k in rr)
-                gn = [sum_in_order(phi[i][k] * g[k] for k in rr) for i in rr]
-                noise = ty(self._sigma2[j]) + s
-                d = (a - big_g[0][0]) + noise
-                v = (md[:, j] - ty(self.data[j])) - gn[0]
-                bad |= ~np.isfinite(md[:, j]) | ~((d > 0) & (d < np.inf))
-                inv_d = 1 / d
-                u = [a - big_g[0][0], -big_g[1][0] if states > 1 else None,
-                     a * -(1 / ty(3)) - big_g[2][0] if states > 2 else None]
-                k = [u[i] * inv_d for i in rr]
-                g = [gn[i] + k[i] * v for i in rr]
-                for i in rr:
-                    for c in range(i + 1):
-                        big_g[i][c] = big_g[c][i] = big_g[i][c] + u[i] * k[c]
-                # G00 + u0 k0 in the form that is a exactly without noise
-                big_g[0][0] = a - noise * k[0]
-                y = (v * v) * inv_d - q_low          # a compensated sum
-                q_new = q_sum + y
-                q_low = (q_new - q_sum) - y
-                q_sum = q_new
-                l_sum = l_sum + np.log(d)
-            out = ty(self.log_norm) - ty(0.5) * (q_sum + l_sum)
-        out = np.where(bad, ty(np.nan), out)
-        return out
-
-    def _numpy_terms(self, m, h, ty):
-        """The recursion of nb_gps_terms.hip for a sum of terms, with its
-        operations in its order: the slots' blocks of the state one after the
-        other, every sum over slots in slot order."""
-        n, p = m.shape
-        slots = self._slots
-        sizes = [GPS_STATES[name] for name, _ in slots]
+            slots = [(name, col, col + 2) for name, col in self._slots]
+            col_s = self._width - 1
+        else:
+            slots, col_s = [(self.kernel, 0, 3)], 2
+        sizes = [GPS_STATES[name] for name, _, _ in slots]
         offs = [sum(sizes[:i]) for i in range(len(slots))]
         rs = range(sum(sizes))
         with np.errstate(all='ignore'):
-            s = h[:, -1].astype(ty)
+            s = h[:, col_s].astype(ty)
             bad = ~((s >= 0) & (s < np.inf))
             rows = []                            # a, 1 / l, w, eta, 1 / eta
-            for name, col in slots:
+            for name, col, col_q in slots:
                 a, l = h[:, col].astype(ty), h[:, col + 1].astype(ty)
                 bad |= ~((a >= 0) & (a < np.inf)) | ~((l > 0) & (l < np.inf))
                 inv_l = np.minimum(1 / l, ty(np.finfo(np.float64).max))
                 w = eta = inv_eta = None
                 if name == 'sho':
-                    q = h[:, col + 2].astype(ty)
+                    q = h[:, col_q].astype(ty)
                     bad |= ~((q > 0.5) & (q < np.inf))
                     w = 1 / (2 * q)
                     eta = np.sqrt(1 - w * w)
@@ -1290,9 +1235,9 @@ class GaussianProcessSeriesLikelihood(_ModelLikelihood):
             md = m.astype(ty)
             for j in range(p):
                 phis = [self._transition(
-                    np.minimum(ty(self._dt[j]) * inv_l, ty(GPS_CAP)), w, eta,
-                    inv_eta, name)
-                    for (name, _), (_, inv_l, w, eta, inv_eta)
+                    name, np.minimum(ty(self._dt[j]) * inv_l, ty(GPS_CAP)), w,
+                    eta, inv_eta)
+                    for (name, _, _), (_, inv_l, w, eta, inv_eta)
                     in zip(slots, rows)]
                 # 1. the lower blocks, mirrored; then g
                 for bi, (oi, ri, phi_i) in enumerate(zip(offs, sizes, phis)):
@@ -1336,6 +1281,9 @@ class GaussianProcessSeriesLikelihood(_ModelLikelihood):
                 for i in rs:
                     for c in range(i + 1):
                         big_g[i][c] = big_g[c][i] = big_g[i][c] + u[i] * k[c]
+                if len(slots) == 1:
+                    # G00 + u0 k0 in the form that is a exactly without noise
+                    big_g[0][0] = rows[0][0] - noise * k[0]
                 # 6.
                 y = (v * v) * inv_d - q_low          # a compensated sum
                 q_new = q_sum + y

@@ -1,5 +1,5 @@
 # Gaussian-process likelihood of an ordered series with a SUM of kernel terms
-# (nb_gps_create_terms / nb_gps_loglike, nb_gps_terms.hip) on one GPU, next to
+# (nb_gps_create_terms / nb_gps_loglike, nb_gps_filter.h) on one GPU, next to
 # gps_bench.py:
 #  * time per call at n = 8192 and P = 128, 1024, 16384 for composite kernels
 #    and, in the same run, for the single-term 'matern52' and 'sho', with the

@@ -1,6 +1,6 @@
 """The device Gaussian-process likelihood of an ordered series
-(``nb_gps_loglike``, nautilus_amd/csrc/nb_gps.hip) against its recursion in
-``np.longdouble``, its bit-for-bit independence of the batch, its NaN rules,
+(``nb_gps_loglike``, nautilus_amd/csrc/nb_gps_filter.h) against its recursion
+in ``np.longdouble``, its bit-for-bit independence of the batch, its NaN rules,
 the dense kernel ``nb_gp_loglike`` on the same inputs, a series of 2^20
 samples, and end to end through ``Sampler``.  The problems, the truth and the
 tolerance (``case_budget``: eight times the float64 twin's own error against

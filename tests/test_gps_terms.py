@@ -1,5 +1,5 @@
 """``GaussianProcessSeriesLikelihood`` with a sum of kernel terms, without a
-GPU: the numpy twin of the recursion of nb_gps_terms.hip against a dense
+GPU: the numpy twin of the recursion of nb_gps_filter.h against a dense
 Cholesky factorisation of the defining covariance in ``np.longdouble`` and
 against LAPACK on the same matrix, the invariance under the order of the
 terms, switched-off terms, the NaN rules and what the constructor refuses.

@@ -1,6 +1,6 @@
 """The device Gaussian-process likelihood of an ordered series with a sum of
 kernel terms (``nb_gps_create_terms`` / ``nb_gps_loglike``,
-nautilus_amd/csrc/nb_gps_terms.hip) against its recursion in
+nautilus_amd/csrc/nb_gps_filter.h) against its recursion in
 ``np.longdouble``, its bit-for-bit independence of the batch and of the order
 of the terms, its NaN rules, the dense kernel ``nb_gp_loglike`` and the
 single-term kernel on the same inputs, its C ABI, and end to end through

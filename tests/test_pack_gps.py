@@ -2,9 +2,9 @@
 (``pack_gps`` of nautilus_amd/csrc/nb_pack.h, all of ``nb_gps_create`` but the
 upload), built for the host by tests/gps_pack_check.cpp.  The layout of
 nb_layout.h is written out again here in numpy, from the reading side: for
-every double the kernel of nb_gps.hip reads, the number that has to be there.
-Every refusal returns its code and its message.  The same program runs once
-more under the address and undefined-behaviour sanitizers."""
+every double the filter of nb_gps_filter.h reads, the number that has to be
+there.  Every refusal returns its code and its message.  The same program
+runs once more under the address and undefined-behaviour sanitizers."""
 
 import os
 import shutil
@@ -86,7 +86,7 @@ def inputs(p):
 
 
 def read_side(p, t=None, with_sigma2=True):
-    """The table as the kernel reads it (nb_gps.hip, the step loop): datum j
+    """The table as the kernel reads it (nb_gps_filter.h, the step loop): datum j
     at doubles 4 j .. 4 j + 3: the step t_j - t_j-1 (0 at j = 0), d_j,
     sigma_j^2 and a zero."""
     t0, data, sigma2 = inputs(p)

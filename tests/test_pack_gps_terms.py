@@ -1,11 +1,12 @@
 """The argument checks and the slot plan of the Gaussian-process series
-likelihood of a sum of terms (``plan_gps_terms`` of
-nautilus_amd/csrc/nb_pack.h, all of ``nb_gps_create_terms`` but ``pack_gps``
-and the upload), built for the host by tests/gps_terms_check.cpp.  The plan
-is written out again here from the reading side -- where nb_gps_terms.hip
-finds every slot -- for every sequence of two or three kernel codes; every
-refusal returns its code and its own message.  The same program runs once
-more under the address and undefined-behaviour sanitizers."""
+likelihood (``plan_gps_terms`` of nautilus_amd/csrc/nb_pack.h for a sum of
+terms, all of ``nb_gps_create_terms`` but ``pack_gps`` and the upload, and
+``plan_gps_one`` for one term), built for the host by
+tests/gps_terms_check.cpp.  The plan is written out again here from the
+reading side -- where the filter of nb_gps_filter.h finds every slot -- for
+each of the four kernels alone and for every sequence of two or three kernel
+codes; every refusal returns its code and its own message.  The same program
+runs once more under the address and undefined-behaviour sanitizers."""
 
 import itertools
 import os
@@ -75,20 +76,34 @@ def sequences():
 def read_side(codes):
     """What the kernel is told: slot I is the I-th term in a stable sort by
     kernel code, with the column of its a in a row that holds the terms in
-    the caller's order, then s."""
+    the caller's order, then s; the column of a sho's q is two after that of
+    its a, and 0 (not read) for the other kernels."""
     first = [sum(COLUMNS[c] for c in codes[:i]) for i in range(len(codes))]
     order = sorted(range(len(codes)), key=lambda i: codes[i])
     width = sum(COLUMNS[c] for c in codes) + 1
     numbers = [len(codes)] + [codes[i] for i in order] + \
-        [first[i] for i in order] + [width - 1, width,
-                                     sum(STATES[c] for c in codes)]
+        [first[i] for i in order] + \
+        [first[i] + 2 if codes[i] == 3 else 0 for i in order] + \
+        [width - 1, width, sum(STATES[c] for c in codes)]
+    return ' '.join(map(str, numbers))
+
+
+def read_side_one(code):
+    """One term's row is (a, l, s[, q]): a in column 0, s in column 2 and a
+    sho's q in column 3."""
+    from nautilus_amd import device
+    names = {v: k for k, v in device.GPS_KERNELS.items()}
+    width = device.gps_width(names[code])
+    assert width == (4 if code == 3 else 3)
+    numbers = [1, code, 0, 3 if code == 3 else 0, 2, width, STATES[code]]
     return ' '.join(map(str, numbers))
 
 
 def test_cases(checked):
     names = {'k' + ''.join(map(str, c)) for c in sequences()}
     assert len(names) == 16 + 64
-    assert set(checked) == names | set(REFUSALS)
+    ones = {'one%d' % c for c in range(4)}
+    assert set(checked) == names | ones | set(REFUSALS)
 
 
 def test_every_slot_sits_where_the_kernel_reads_it(checked):
@@ -104,9 +119,25 @@ def test_every_slot_sits_where_the_kernel_reads_it(checked):
         accepted.add(tuple(sorted(codes)))
     assert len(accepted) == 23
     assert len([c for c in accepted if len(c) == 2]) == 10
-    # written out: sho, exp, sho is slots exp (column 3), sho (0), sho (5)
-    assert checked['k303'][1] == '3 0 3 3 3 0 5 8 9 5'
-    assert checked['k21'][1] == '2 1 2 2 0 4 5 5'
+    # written out: sho, exp, sho is slots exp (column 3), sho (0), sho (5),
+    # with the q of the two sho in columns 2 and 7
+    assert checked['k303'][1] == '3 0 3 3 3 0 5 0 2 7 8 9 5'
+    assert checked['k21'][1] == '2 1 2 2 0 0 0 4 5 5'
+
+
+def test_one_term_sits_where_the_kernel_reads_it(checked):
+    """``plan_gps_one``: the plan of ``nb_gps_create`` for each of the four
+    kernels, with the width of ``device.gps_width``."""
+    from nautilus_amd import device
+    for code in range(4):
+        assert checked['one%d' % code] == (0, read_side_one(code), 20, ''), \
+            code
+    assert sorted(device.GPS_KERNELS.values()) == [0, 1, 2, 3]
+    # written out: (a, l, s) and, for sho, (a, l, s, q)
+    assert checked['one0'][1] == '1 0 0 0 2 3 1'
+    assert checked['one1'][1] == '1 1 0 0 2 3 2'
+    assert checked['one2'][1] == '1 2 0 0 2 3 3'
+    assert checked['one3'][1] == '1 3 0 3 2 4 2'
 
 
 def test_refusals(checked):
