@@ -113,18 +113,20 @@ constexpr int nb_mixture_record(int dt) {
 // Operand tile of the likelihoods that stream model rows (nb_chi2.hip,
 // nb_fold.hip): element (row l, column c) of a 16x16 tile; lane group c / 4 of
 // k-step c % 4 holds column c (what a staging thread of the kernel reads as
-// 32 contiguous bytes of a model row)
+// 32 contiguous bytes of a model row).  The matrix of such a likelihood is
+// stored as operand tiles, zero padded, in PANEL ORDER, the order the panel
+// driver (nb_panel.h) walks them: panels of NB_PANEL_TILES row tiles; per
+// panel its k-tiles (all of them, or of a lower-triangular matrix 0 .. the
+// panel's last row tile); per k-tile the panel's row tiles.
 constexpr int nb_operand_index(int l, int c) {
   return (c & 3) * 64 + (c >> 2) * 16 + l;
 }
+#define NB_PANEL_TILES 16
 
 // Gaussian likelihood of a data vector (nb_chi2.hip).  Full covariance: the
 // blob is d zero padded to 16 DT doubles (rounded up to the 1 KB of a
-// global_load_lds piece), then W = L^-1 as 16x16 operand tiles in the order
-// the kernel walks them: panels of NB_CHI2_PANEL row tiles; per panel the
-// k-tiles 0 .. its last row tile; per k-tile the panel's row tiles.  Diagonal
-// covariance: d [P], then 1 / sigma [P].
-#define NB_CHI2_PANEL 16
+// global_load_lds piece), then the lower triangle of W = L^-1 in panel order.
+// Diagonal covariance: d [P], then 1 / sigma [P].
 constexpr int nb_chi2_w_offset(int dt) {
   return (16 * dt + 127) / 128 * 128;
 }
@@ -137,10 +139,7 @@ constexpr int nb_chi2_w_offset(int dt) {
 //
 // Poisson likelihood behind a response matrix (nb_fold.hip).  The blob is the
 // Poisson table with each array zero padded to 16 DT doubles (1 for the
-// exposure), then R (P x K) as 16x16 operand tiles, zero padded, in the order
-// the kernel walks them: panels of NB_FOLD_PANEL row tiles; per panel every
-// k-tile; per k-tile the panel's row tiles.
-#define NB_FOLD_PANEL 16
+// exposure), then all of R (P x K) in panel order.
 constexpr size_t nb_fold_r_offset(int dt) {
   return 64 * (size_t)dt;
 }

@@ -592,6 +592,41 @@ int pack_mixture(int32_t n_dim, int32_t n_components, const double* means,
   return NB_OK;
 }
 
+// Appends the rows x cols matrix a (row-major, leading dimension ld) to the
+// image as operand tiles in panel order, zero padded (nb_layout.h,
+// nb_operand_index); lower: the lower triangle only, the k-tiles of a panel
+// ending at its last row tile
+void put_panel_tiles(std::vector<double>* image, const double* a, size_t ld,
+                     size_t rows, size_t cols, bool lower) {
+  const int dt = (int)((rows + 15) / 16);
+  const auto k_tiles = [&](int pn) {
+    return lower ? std::min(NB_PANEL_TILES * (pn + 1), dt)
+                 : (int)((cols + 15) / 16);
+  };
+  const auto row_tiles = [&](int pn) {
+    return std::min(NB_PANEL_TILES, dt - NB_PANEL_TILES * pn);
+  };
+  const int n_panels = (dt + NB_PANEL_TILES - 1) / NB_PANEL_TILES;
+  size_t tiles = 0;
+  for (int pn = 0; pn < n_panels; ++pn)
+    tiles += (size_t)row_tiles(pn) * (size_t)k_tiles(pn);
+  const size_t at = image->size();
+  image->resize(at + tiles * NB_TILE, 0.0);
+  double* tile = image->data() + at;
+  for (int pn = 0; pn < n_panels; ++pn)
+    for (int kt = 0; kt < k_tiles(pn); ++kt)
+      for (int ti = 0; ti < row_tiles(pn); ++ti, tile += NB_TILE)
+        for (int l = 0; l < 16; ++l) {
+          const size_t h = 16 * (size_t)(NB_PANEL_TILES * pn + ti) + l;
+          if (h >= rows) break;
+          for (int c = 0; c < 16; ++c) {
+            const size_t k = 16 * (size_t)kt + c;
+            if (k < cols && (!lower || k <= h))
+              tile[nb_operand_index(l, c)] = a[h * ld + k];
+          }
+        }
+}
+
 // Data vector and W = L^-1 (or 1 / sigma) for nb_chi2.hip (nb_layout.h,
 // nb_chi2_w_offset)
 int pack_chi2(int32_t n_data, const double* data, const double* chol_inv,
@@ -634,31 +669,9 @@ int pack_chi2(int32_t n_data, const double* data, const double* chol_inv,
         return NB_ERR_ARG;
       }
     }
-  const int dt = (n_data + 15) / 16;
-  const int n_panels = (dt + NB_CHI2_PANEL - 1) / NB_CHI2_PANEL;
-  size_t tiles = 0;
-  for (int pn = 0; pn < n_panels; ++pn) {
-    const int nrt = std::min(NB_CHI2_PANEL, dt - NB_CHI2_PANEL * pn);
-    tiles += (size_t)nrt * (size_t)(NB_CHI2_PANEL * pn + nrt);
-  }
-  host.assign((size_t)nb_chi2_w_offset(dt) + tiles * NB_TILE, 0.0);
+  host.assign((size_t)nb_chi2_w_offset((n_data + 15) / 16), 0.0);
   for (size_t k = 0; k < p; ++k) host[k] = data[k];
-  double* tile = host.data() + nb_chi2_w_offset(dt);
-  for (int pn = 0; pn < n_panels; ++pn) {
-    const int nrt = std::min(NB_CHI2_PANEL, dt - NB_CHI2_PANEL * pn);
-    for (int kt = 0; kt < NB_CHI2_PANEL * pn + nrt; ++kt)
-      for (int ti = 0; ti < nrt; ++ti, tile += NB_TILE) {
-        const int rt = NB_CHI2_PANEL * pn + ti;
-        if (kt > rt) continue;                 // above the diagonal: zeros
-        for (int c = 0; c < 16; ++c)
-          for (int l = 0; l < 16; ++l) {
-            const size_t h = 16 * (size_t)rt + l;
-            const size_t k = 16 * (size_t)kt + c;
-            if (h < p && k <= h)
-              tile[nb_operand_index(l, c)] = chol_inv[h * p + k];
-          }
-      }
-  }
+  put_panel_tiles(&host, chol_inv, p, p, p, true);
   return NB_OK;
 }
 
@@ -733,10 +746,10 @@ int pack_fold_poisson(int32_t n_data, int32_t n_src, const double* counts,
     return NB_ERR_ARG;
   }
   const size_t p = (size_t)n_data, ks = (size_t)n_src;
-  const int dt = (n_data + 15) / 16, nkt = (n_src + 15) / 16;
+  const int dt = (n_data + 15) / 16;
   const size_t pp = 16 * (size_t)dt;             // padded table arrays
   std::vector<double>& host = *image;
-  host.assign(nb_fold_r_offset(dt) + (size_t)dt * (size_t)nkt * NB_TILE, 0.0);
+  host.assign(nb_fold_r_offset(dt), 0.0);
   for (size_t j = 0; j < pp; ++j) host[2 * pp + j] = 1.0;
   for (size_t j = 0; j < p; ++j) {
     const double k = counts[j];
@@ -753,22 +766,7 @@ int pack_fold_poisson(int32_t n_data, int32_t n_src, const double* counts,
         return NB_ERR_ARG;
       }
   }
-  double* tile = host.data() + nb_fold_r_offset(dt);
-  const int n_panels = (dt + NB_FOLD_PANEL - 1) / NB_FOLD_PANEL;
-  for (int pn = 0; pn < n_panels; ++pn) {
-    const int nrt = std::min(NB_FOLD_PANEL, dt - NB_FOLD_PANEL * pn);
-    for (int kt = 0; kt < nkt; ++kt)
-      for (int ti = 0; ti < nrt; ++ti, tile += NB_TILE)
-        for (int l = 0; l < 16; ++l) {
-          const size_t h = 16 * (size_t)(NB_FOLD_PANEL * pn + ti) + l;
-          if (h >= p) break;
-          const double* row = response + h * (size_t)ld_response;
-          for (int c = 0; c < 16; ++c) {
-            const size_t k = 16 * (size_t)kt + c;
-            if (k < ks) tile[nb_operand_index(l, c)] = row[k];
-          }
-        }
-  }
+  put_panel_tiles(&host, response, (size_t)ld_response, p, ks, false);
   return NB_OK;
 }
 

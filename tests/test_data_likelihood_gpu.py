@@ -149,7 +149,7 @@ def test_values_sigma(p, n):
            what='P = %d, sigma, normalised' % p)
 
 
-@pytest.mark.parametrize('p', [3, 129, 1025])
+@pytest.mark.parametrize('p', [3, 129, 257, 1025])
 @pytest.mark.parametrize('diag', [False, True], ids=['cov', 'sigma'])
 def test_ragged_batches_bit_for_bit(p, diag):
     """Any slice of a batch, taken at an odd row offset, gives the bits the
@@ -189,6 +189,13 @@ def test_ragged_batches_bit_for_bit(p, diag):
         assert torch.equal(like.from_model(reps), torch.cat([full] * 17))
         assert torch.equal(like.from_model(reps[:20000]),
                            torch.cat([full] * 10))
+    # ... and walks a second panel of W with them: 32 768 rows are the first
+    # batch of the largest block, 16 384 of the middle one
+    if not diag and p == 257:
+        reps = torch.cat([big] * 17)[:32768]
+        want = torch.cat([full] * 17)[:32768]
+        assert torch.equal(like.from_model(reps), want)
+        assert torch.equal(like.from_model(reps[:16384]), want[:16384])
 
 
 @pytest.mark.parametrize('p', [17, 129])
