@@ -635,6 +635,43 @@ int nb_noise_loglike(const nb_noise* h, int32_t mode, const double* model_dev,
                      int64_t n, double* out_dev, void* stream);
 int nb_noise_destroy(nb_noise* h);
 
+/* Gaussian likelihood of P measurements d with outliers (the user-side
+ * callable of sampler.py:863-873 for a model prediction m(theta) where every
+ * measurement is either good, with the model's mean and variance, or bad,
+ * drawn from a broad distribution whose fraction, mean and width are free
+ * parameters), one streaming launch that reads every model row once and the
+ * table (d, sigma2) of an nb_noise handle:
+ *   out_dev[i] = log_norm + sum_j log[ (1 - p_i) v_ij^-1/2 exp(e1_ij)
+ *                                      +    p_i  u_ij^-1/2 exp(e2_ij) ],
+ *   v_ij = c_i sigma2_j + a_i + f_i m_ij^2,  e1_ij = -(m_ij - d_j)^2 / (2 v_ij),
+ *   u_ij = sigma2_j + s_i,                   e2_ij = -(d_j - b_i)^2 / (2 u_ij),
+ * row i of the mixture holding the NB_OUTLIER_WIDTH doubles (c_i, a_i, f_i,
+ * p_i, b_i, s_i).  With log_norm = -(P/2) log 2 pi the result is sum_j log
+ * [ (1 - p) N(d_j | m_ij, v_ij) + p N(d_j | b_i, u_ij) ].  Per element no log
+ * and one exp of an argument <= 0: the component with the larger exponent
+ * among those with a non-zero weight is taken out, log q = e_hi + log (A_hi +
+ * A_lo exp(e_lo - e_hi)), the second terms are multiplied by their mantissas
+ * as nb_noise_loglike does with v, so no element underflows however many
+ * sigma away it lies; p = 0 and p = 1 give the one-component value whatever
+ * the other component's exponent is.
+ * nb_outlier_loglike (sampler.py:863-873) only launches, on the caller's
+ * stream (one handle serves any number of streams and both entries): row i of
+ * the model is the n_data doubles at model_dev + i * ld, row i of the mixture
+ * the 6 doubles at mix_dev + i * ld_mix.  NB_ERR_ARG: a NULL handle, n < 0,
+ * ld < n_data or ld_mix < NB_OUTLIER_WIDTH with n > 1, a NULL pointer with
+ * n > 0.  A row with an m_ij or a b_i that is not finite, a v_ij or a u_ij
+ * that is not in (0, +inf) -- zero, negative, NaN or infinite, whatever
+ * coefficient caused it -- or a p_i outside [0, 1], NaN included, is NaN and
+ * changes no other row.  The bits of a row depend on neither n, its position
+ * in the batch, ld, ld_mix, the stream nor the grid.  n = 0 returns NB_OK
+ * without a launch.  ((m - d)^2 / v and (d - b)^2 / u must stay below the
+ * float64 maximum, v and u at or above 2^-1022, and a p > 0 at or above
+ * 2^-510: what a row beyond any of these gives is not specified.)          */
+#define NB_OUTLIER_WIDTH 6
+int nb_outlier_loglike(const nb_noise* h, const double* model_dev, int64_t ld,
+                       const double* mix_dev, int64_t ld_mix, int64_t n,
+                       double* out_dev, void* stream);
+
 /* Gaussian-process likelihood of P measurements d (the user-side callable of
  * sampler.py:863-873 for a model prediction m(theta) under correlated noise
  * whose covariance depends on the point), one launch with one workgroup per

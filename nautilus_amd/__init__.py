@@ -20,6 +20,7 @@ _LAZY = {
     'GaussianDataLikelihood': 'likelihoods',
     'PoissonDataLikelihood': 'likelihoods',
     'GaussianNoiseLikelihood': 'likelihoods',
+    'GaussianOutlierLikelihood': 'likelihoods',
     'GaussianProcessLikelihood': 'likelihoods',
     'GaussianProcessSeriesLikelihood': 'likelihoods',
     'RosenbrockLikelihood': 'likelihoods', 'FunnelLikelihood': 'likelihoods',

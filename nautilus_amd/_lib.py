@@ -188,6 +188,9 @@ _SIGNATURES = {
                                    C.c_int64, C.c_void_p, C.c_int64,
                                    C.c_int64, C.c_void_p, C.c_void_p]),
     'nb_noise_destroy': (C.c_int, [C.c_void_p]),
+    'nb_outlier_loglike': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_void_p, C.c_int64, C.c_int64,
+                                     C.c_void_p, C.c_void_p]),
     'nb_gp_create': (C.c_int, [C.c_int32, c_double_p, c_double_p, c_double_p,
                                C.c_int32, C.c_double, C.POINTER(C.c_void_p)]),
     'nb_gp_loglike': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,

@@ -853,6 +853,21 @@ int nb_noise_loglike(const nb_noise* h, int32_t mode, const double* model,
                          n, h->log_norm, out, as_stream(stream));
 }
 
+// nb_outlier.hip reads the table of nb_noise.hip
+int nb_outlier_loglike(const nb_noise* h, const double* model, int64_t ld,
+                       const double* mix, int64_t ld_mix, int64_t n,
+                       double* out, void* stream) {
+  if (h == nullptr || n < 0 ||
+      (n > 1 && (ld < h->n_data || ld_mix < NB_OUTLIER_WIDTH)) ||
+      (n > 0 && (model == nullptr || mix == nullptr || out == nullptr))) {
+    nb_set_error("bad outlier likelihood arguments (a handle, n >= 0, ld >= "
+                 "n_data, ld_mix >= %d, no NULL pointer)", NB_OUTLIER_WIDTH);
+    return NB_ERR_ARG;
+  }
+  return nb_launch_outlier(h->dev, h->n_data, model, ld, mix, ld_mix, n,
+                           h->log_norm, out, as_stream(stream));
+}
+
 // Data, sigma^2 and the distance tiles for nb_gp.hip (nb_layout.h,
 // nb_gp_tile), uploaded once.
 struct nb_gp {

@@ -69,6 +69,10 @@ int nb_launch_noise(const double* tab, int n_data, int mode,
                     const double* model, long long ld, const double* noise,
                     long long ld_noise, long long n, double log_norm,
                     double* out, hipStream_t stream);
+int nb_launch_outlier(const double* tab, int n_data, const double* model,
+                      long long ld, const double* mix, long long ld_mix,
+                      long long n, double log_norm, double* out,
+                      hipStream_t stream);
 int nb_launch_gp(const double* tab, int n_data, int kernel, int mode,
                  const double* model, long long ld, const double* cov,
                  long long ld_cov, long long n, double log_norm, double* out,

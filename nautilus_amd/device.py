@@ -799,6 +799,20 @@ def noise_launch_shape(n_data):
     return 64, 1, 4
 
 
+OUTLIER_WIDTH = 6                  # NB_OUTLIER_WIDTH
+
+
+def outlier_launch_shape(n_data):
+    """(L, R, U) of ``nb_outlier_loglike`` at P = ``n_data`` (nb_outlier.hip,
+    ``nb_launch_outlier``), with the meaning and the addition count of
+    ``noise_launch_shape``."""
+    if n_data <= 32:
+        return 16, 4, 1
+    if n_data <= 512:
+        return 16, 2, 2
+    return 64, 1, 4
+
+
 class NoiseTable(_Table):
     """Device-resident measurements of a Gaussian likelihood whose variance
     depends on the point (``nb_noise_create``): ``data`` (P,) finite and
@@ -826,6 +840,19 @@ class NoiseTable(_Table):
         return self._rows_loglike(
             self._lib.nb_noise_loglike, (model, self.n_data, ld),
             (noise, noise.shape[1], ld_noise), head=(mode,))
+
+    def outlier_loglike(self, model, mix, ld=None, ld_mix=None):
+        """log L of the two-component outlier mixture (``nb_outlier_loglike``,
+        on this table's data and sigma^2) of the rows of the cuda float64
+        tensors ``model`` (n, P) and ``mix`` (n, 6) with columns (c, a, f, p,
+        b, s), both read in place (``_rows_loglike``)."""
+        n = model.shape[0]
+        if mix.shape[0] != n:
+            raise ValueError('model and mixture must have the same number of '
+                             'rows, not %d and %d' % (n, mix.shape[0]))
+        return self._rows_loglike(
+            self._lib.nb_outlier_loglike, (model, self.n_data, ld),
+            (mix, OUTLIER_WIDTH, ld_mix))
 
 
 GP_HYPER, GP_FULL = 0, 1           # NB_GP_HYPER, NB_GP_FULL

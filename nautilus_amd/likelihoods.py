@@ -723,6 +723,154 @@ class GaussianNoiseLikelihood(_ModelLikelihood):
         return out
 
 
+class GaussianOutlierLikelihood(_ModelLikelihood):
+    """Gaussian likelihood of independent measurements some of which are
+    outliers -- the two-component mixture per measurement of Hogg, Bovy &
+    Lang (2010): a measurement is either good, with the model's mean and
+    variance, or bad, drawn from a broad Gaussian whose fraction, mean and
+    width are free parameters:
+
+        log L(theta) = log_norm + sum_j log[
+            (1 - p) v_j^-1/2 exp(-(m_j - d_j)^2 / (2 v_j))
+            +    p  u_j^-1/2 exp(-(d_j - b)^2 / (2 u_j)) ],
+
+    ``log_norm = -(P/2) log 2 pi``, or 0 with ``normalised=False``.
+
+    ``data`` holds the P finite measurements, P at most 2^20; ``sigma`` the P
+    quoted error bars, finite and >= 0 (``None`` = all zero).  ``model`` takes
+    the (n, n_dim) batch of points as a torch tensor and returns a pair
+    ``(m, w)`` of float64 tensors on the same device: ``m`` the (n, P)
+    predictions and ``w`` (n, 6) with columns (c, a, f, p, b, s),
+
+      v_ij = c_i sigma_j^2 + a_i + f_i m_ij^2   the inlier variance, the
+                                                expression of
+                                                ``GaussianNoiseLikelihood``
+                                                with noise='row';
+      u_ij = sigma_j^2 + s_i                    the outlier variance;
+      p_i in [0, 1]                             the outlier fraction;
+      b_i                                       the outlier mean.
+
+    A call evaluates the model and then runs the fused kernel
+    ``nb_outlier_loglike`` -- one streaming launch on the current stream that
+    reads every row once, takes no log and one exp per element and never
+    underflows: the component with the larger exponent is taken out of the
+    sum, so a measurement hundreds of sigma away from the model costs what
+    the outlier component says and not ``-inf``.  ``p = 0`` and ``p = 1`` give
+    the one-component value.  ``from_model`` is the second half alone, with
+    the layout rules of ``GaussianNoiseLikelihood.from_model``.  ``numpy`` /
+    ``numpy_from_model`` are the pure-numpy twins, ``numpy_terms`` the two
+    weighted log densities of every measurement and
+    ``numpy_responsibilities`` the posterior probability that a measurement
+    is an outlier (host only; for posterior samples).
+
+    Row i is NaN when any m_ij or b_i is not finite, any v_ij or u_ij is not
+    in (0, +inf), or p_i is outside [0, 1], NaN included.  That changes no bit
+    of any other row."""
+
+    _pair = True
+    _what = 'the model output and the mixture'
+
+    def __init__(self, model, data, sigma=None, *, normalised=True):
+        super().__init__(model)
+        data = _bounded_vector(data, 'data', N_NOISE_MAX, 'data points')
+        if not np.all(np.isfinite(data)):
+            raise ValueError('data must be finite')
+        self.data = data.copy()
+        self.n_data = p = len(data)
+        if sigma is None:
+            self.sigma = np.zeros(p)
+        else:
+            self.sigma = _numbers(sigma, p, 'sigma', False).copy()
+        with np.errstate(over='ignore'):
+            self._sigma2 = self.sigma * self.sigma
+        if not np.all(np.isfinite(self._sigma2)):
+            raise ValueError('sigma is too large: sigma^2 is not finite')
+        self.log_norm = -0.5 * p * np.log(2 * np.pi) if normalised else 0.0
+
+    def _make_table(self):
+        return device.NoiseTable(self.data, self._sigma2,
+                                 log_norm=self.log_norm)
+
+    def _widths(self):
+        return self.n_data, device.OUTLIER_WIDTH
+
+    def _loglike(self, m, w):
+        return self._table().outlier_loglike(m, w)
+
+    def _check(self, m, w):
+        super()._check(m)
+        width = device.OUTLIER_WIDTH
+        if w.ndim != 2 or tuple(w.shape) != (m.shape[0], width):
+            raise ValueError('the mixture must have shape (%d, %d), not %s' %
+                             (m.shape[0], width, tuple(w.shape)))
+
+    def from_model(self, m, w):
+        """log L of the rows of an (n, P) float64 model output and its (n, 6)
+        mixture coefficients: cuda tensors in, a cuda tensor out; numpy in,
+        numpy out."""
+        if isinstance(m, torch.Tensor) != isinstance(w, torch.Tensor):
+            raise ValueError('the model output and the mixture must both be '
+                             'torch tensors or both numpy arrays')
+        return self._from_outputs(m, w)
+
+    def _parts(self, m, w):
+        """(e1, e2, A1, A2, bad) of an (n, P) model output and its mixture in
+        pure numpy: the two exponents, the two amplitudes (1 - p) v^-1/2 and
+        p u^-1/2, and where an element makes its row NaN; there the other
+        four are those of a standard normal at its mean."""
+        m, w = np.asarray(m, float), np.asarray(w, float)
+        self._check(m, w)
+        c, a, f, p, b, s = (w[:, i:i + 1] for i in range(6))
+        with np.errstate(all='ignore'):
+            v = c * self._sigma2 + a + f * (m * m)
+            u = self._sigma2 + s
+            bad = ~(np.isfinite(m) & (v > 0) & (v < np.inf) & (u > 0) &
+                    (u < np.inf) & (p >= 0) & (p <= 1) & np.isfinite(b))
+            yv = 1.0 / np.sqrt(np.where(bad, 1.0, v))
+            yu = 1.0 / np.sqrt(np.where(bad, 1.0, u))
+            r1 = np.where(bad, 0.0, m - self.data)
+            r2 = np.where(bad, 0.0, self.data - b)
+            e1 = -0.5 * ((r1 * r1) * (yv * yv))
+            e2 = -0.5 * ((r2 * r2) * (yu * yu))
+            a1 = np.where(bad, 1.0, (1.0 - p) * yv)
+            a2 = np.where(bad, 0.0, p * yu)
+        return e1, e2, a1, a2, bad
+
+    def numpy_terms(self, m, w):
+        """The (n, P) pair of weighted log densities log[(1 - p) v^-1/2] -
+        (m - d)^2 / (2 v) and log[p u^-1/2] - (d - b)^2 / (2 u) in pure
+        numpy, without the constant: ``-inf`` where the weight is zero, NaN
+        where the element makes its row NaN."""
+        e1, e2, a1, a2, bad = self._parts(m, w)
+        with np.errstate(divide='ignore'):
+            l1 = np.where(bad, np.nan, e1 + np.log(a1))
+            l2 = np.where(bad, np.nan, e2 + np.log(a2))
+        return l1, l2
+
+    def numpy_responsibilities(self, m, w):
+        """The (n, P) posterior probabilities that measurement j is an outlier
+        at point i, p N(d | b, u) / [(1 - p) N(d | m, v) + p N(d | b, u)], in
+        pure numpy (host only: made for posterior samples); NaN where the
+        element makes its row NaN."""
+        l1, l2 = self.numpy_terms(m, w)
+        with np.errstate(all='ignore'):
+            return np.exp(l2 - np.logaddexp(l1, l2))
+
+    def numpy_from_model(self, m, w):
+        """Pure-numpy evaluation of an (n, P) model output and its mixture
+        (CPU baseline / oracle runs / tests), in the arithmetic of the
+        kernel: log q = e_hi + log(A_hi + A_lo exp(e_lo - e_hi))."""
+        e1, e2, a1, a2, bad = self._parts(m, w)
+        with np.errstate(all='ignore'):
+            one = (a2 == 0.0) | ((a1 != 0.0) & (e1 >= e2))
+            e_hi, e_lo = np.where(one, e1, e2), np.where(one, e2, e1)
+            a_hi, a_lo = np.where(one, a1, a2), np.where(one, a2, a1)
+            big_b = a_hi + a_lo * np.exp(np.minimum(e_lo - e_hi, 0.0))
+            out = self.log_norm + np.sum(e_hi + np.log(big_b), axis=1)
+        out[np.any(bad, axis=1)] = np.nan
+        return out
+
+
 N_GP_MAX = 128                     # NB_GP_MAX_DATA of nautilus_hip.h
 GP_KERNELS = ('sqexp', 'exp', 'matern32', 'matern52')
 
