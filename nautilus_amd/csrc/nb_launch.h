@@ -6,6 +6,30 @@
 
 #include "nb_common.h"
 
+// The launch shape of the row-streaming kernels (nb_poisson_kernel,
+// nb_rowprod_kernel): L lanes share a row, a lane group walks R rows and U
+// column blocks of L per step, workgroups of 256 lanes.
+template <int L_, int R_, int U_>
+struct nb_stream_shape {
+  static constexpr int L = L_, R = R_, U = U_;
+  static unsigned grid(long long n) {            // workgroups for n rows
+    constexpr long long rows = (256 / L) * R;    // of a workgroup per step
+    const long long b = (n + rows - 1) / rows;
+    return (unsigned)(b > 8192 ? 8192 : b);
+  }
+};
+
+// launch(shape) with the shape of P = n_data.  It is a function of P alone (a
+// row's bits depend on it): short rows put their independent work into
+// several rows per lane, long rows into column blocks of a whole wavefront.
+// device.stream_launch_shape repeats it for the tests' error budgets.
+template <class F>
+int nb_stream_dispatch(int n_data, F launch) {
+  if (n_data <= 32) return launch(nb_stream_shape<16, 4, 1>());
+  if (n_data <= 512) return launch(nb_stream_shape<16, 2, 2>());
+  return launch(nb_stream_shape<64, 1, 4>());
+}
+
 bool nb_eval_fast_eligible(int n_dim, int K, int M, int E, bool sample);
 int nb_launch_eval_fast(const double* blob_dev, int n_dim, bool sample, int m,
                         int recentre, const double* x, const long long* idx,

@@ -124,32 +124,19 @@ nb_poisson_kernel(const double* __restrict__ tab, int n_data,
   }
 }
 
-template <int L, int R, int U>
-int launch(const double* tab, int n_data, const double* model, long long ld,
-           long long n, double log_const, double* out, hipStream_t stream) {
-  constexpr long long rows = (256 / L) * R;      // of a workgroup per step
-  long long b = (n + rows - 1) / rows;
-  if (b > 8192) b = 8192;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL((nb_poisson_kernel<L, R, U>), dim3((unsigned)b),
-                     dim3(256), 0, stream, tab, n_data, model, ld, n,
-                     log_const, out);
-  NB_HIP_CHECK(hipGetLastError());
-  return NB_OK;
-}
-
 }  // namespace
 
 int nb_launch_poisson(const double* tab, int n_data, const double* model,
                       long long ld, long long n, double log_const,
                       double* out, hipStream_t stream) {
   if (n <= 0) return NB_OK;
-  // the shape is a function of P alone (a row's bits depend on it): short
-  // rows put their independent work into several rows per lane, long rows
-  // into column blocks of a whole wavefront
-  if (n_data <= 32)
-    return launch<16, 4, 1>(tab, n_data, model, ld, n, log_const, out, stream);
-  if (n_data <= 512)
-    return launch<16, 2, 2>(tab, n_data, model, ld, n, log_const, out, stream);
-  return launch<64, 1, 4>(tab, n_data, model, ld, n, log_const, out, stream);
+  return nb_stream_dispatch(n_data, [&](auto s) {
+    using S = decltype(s);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL((nb_poisson_kernel<S::L, S::R, S::U>),
+                       dim3(S::grid(n)), dim3(256), 0, stream, tab, n_data,
+                       model, ld, n, log_const, out);
+    NB_HIP_CHECK(hipGetLastError());
+    return NB_OK;
+  });
 }

@@ -730,6 +730,22 @@ class Chi2Table(_Table):
                                   (model, self.n_data, ld))
 
 
+def stream_launch_shape(n_data):
+    """(L, R, U) of ``nb_poisson_loglike``, ``nb_noise_loglike`` and
+    ``nb_outlier_loglike`` at P = ``n_data`` (nb_launch.h,
+    ``nb_stream_dispatch``): L lanes share a row, R rows and U column blocks
+    per step.  A row's partial sums pass through ceil(P / (L U)) + log2(L U)
+    additions."""
+    if n_data <= 32:
+        return 16, 4, 1
+    if n_data <= 512:
+        return 16, 2, 2
+    return 64, 1, 4
+
+
+noise_launch_shape = outlier_launch_shape = stream_launch_shape
+
+
 class PoissonTable(_Table):
     """Device-resident bins of a Poisson likelihood (``nb_poisson_create``):
     ``counts`` (P,) >= 0, ``exposure`` (P,) > 0 (None = 1) and ``background``
@@ -785,32 +801,7 @@ class FoldedPoissonTable(_Table):
 
 
 NOISE_ROW, NOISE_FULL = 0, 1       # NB_NOISE_ROW, NB_NOISE_FULL
-
-
-def noise_launch_shape(n_data):
-    """(L, R, U) of ``nb_noise_loglike`` at P = ``n_data`` (nb_noise.hip,
-    ``launch_mode``): L lanes share a row, R rows and U column blocks per
-    step.  A row's partial sums pass through ceil(P / (L U)) + log2(L U)
-    additions."""
-    if n_data <= 32:
-        return 16, 4, 1
-    if n_data <= 512:
-        return 16, 2, 2
-    return 64, 1, 4
-
-
 OUTLIER_WIDTH = 6                  # NB_OUTLIER_WIDTH
-
-
-def outlier_launch_shape(n_data):
-    """(L, R, U) of ``nb_outlier_loglike`` at P = ``n_data`` (nb_outlier.hip,
-    ``nb_launch_outlier``), with the meaning and the addition count of
-    ``noise_launch_shape``."""
-    if n_data <= 32:
-        return 16, 4, 1
-    if n_data <= 512:
-        return 16, 2, 2
-    return 64, 1, 4
 
 
 class NoiseTable(_Table):

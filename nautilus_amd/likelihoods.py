@@ -180,6 +180,55 @@ class _ModelLikelihood(_DeviceTables):
             for t in self._outputs(torch.from_numpy(x))])
 
 
+class _PairLikelihood(_ModelLikelihood):
+    """A likelihood of P measurements ``data`` with error bars ``sigma`` whose
+    model returns a pair: the (n, P) prediction and a second output, which
+    ``_second`` names in messages and whose rows are ``_width`` wide."""
+
+    _pair = True
+    _what = property(lambda self: 'the model output and the ' + self._second)
+
+    def _set_data(self, data, n_max):
+        """``data`` and ``n_data``; returns P."""
+        data = _bounded_vector(data, 'data', n_max, 'data points')
+        if not np.all(np.isfinite(data)):
+            raise ValueError('data must be finite')
+        self.data = data.copy()
+        self.n_data = len(data)
+        return self.n_data
+
+    def _set_sigma(self, sigma, normalised):
+        """``sigma``, ``_sigma2`` and ``log_norm``, once ``n_data`` is set."""
+        p = self.n_data
+        if sigma is None:
+            self.sigma = np.zeros(p)
+        else:
+            self.sigma = _numbers(sigma, p, 'sigma', False).copy()
+        with np.errstate(over='ignore'):
+            self._sigma2 = self.sigma * self.sigma
+        if not np.all(np.isfinite(self._sigma2)):
+            raise ValueError('sigma is too large: sigma^2 is not finite')
+        self.log_norm = -0.5 * p * np.log(2 * np.pi) if normalised else 0.0
+
+    def _widths(self):
+        return self.n_data, self._width
+
+    def _second_shape(self, n):
+        return n, self._width
+
+    def _check(self, m, w):
+        super()._check(m)
+        if w.ndim != 2 or tuple(w.shape) != (m.shape[0], self._width):
+            raise ValueError('the %s must have shape %s, not %s' % (
+                self._second, self._second_shape(m.shape[0]),
+                tuple(w.shape)))
+
+    def _same_kind(self, m, w):
+        if isinstance(m, torch.Tensor) != isinstance(w, torch.Tensor):
+            raise ValueError('%s must both be torch tensors or both numpy '
+                             'arrays' % self._what)
+
+
 class GaussianMixtureLikelihood(_DeviceTables):
     """Mixture of Gaussians  log sum_k w_k N(x; mu_k, Sigma_k).
 
@@ -594,7 +643,7 @@ class PoissonDataLikelihood(_ModelLikelihood):
 N_NOISE_MAX = 1 << 20              # NB_NOISE_MAX_DATA of nautilus_hip.h
 
 
-class GaussianNoiseLikelihood(_ModelLikelihood):
+class GaussianNoiseLikelihood(_PairLikelihood):
     """Gaussian likelihood of independent measurements whose error bars carry
     free parameters:
 
@@ -631,8 +680,7 @@ class GaussianNoiseLikelihood(_ModelLikelihood):
     changes no bit of any other row.  The signs of the single coefficients do
     not matter as long as v > 0."""
 
-    _pair = True
-    _what = 'the model output and the noise'
+    _second = 'noise'
 
     def __init__(self, model, data, sigma=None, *, noise='row',
                  normalised=True):
@@ -641,20 +689,8 @@ class GaussianNoiseLikelihood(_ModelLikelihood):
             raise ValueError("noise must be 'row' or 'full', not %r" %
                              (noise,))
         self.noise = noise
-        data = _bounded_vector(data, 'data', N_NOISE_MAX, 'data points')
-        if not np.all(np.isfinite(data)):
-            raise ValueError('data must be finite')
-        self.data = data.copy()
-        self.n_data = p = len(data)
-        if sigma is None:
-            self.sigma = np.zeros(p)
-        else:
-            self.sigma = _numbers(sigma, p, 'sigma', False).copy()
-        with np.errstate(over='ignore'):
-            self._sigma2 = self.sigma * self.sigma
-        if not np.all(np.isfinite(self._sigma2)):
-            raise ValueError('sigma is too large: sigma^2 is not finite')
-        self.log_norm = -0.5 * p * np.log(2 * np.pi) if normalised else 0.0
+        self._set_data(data, N_NOISE_MAX)
+        self._set_sigma(sigma, normalised)
 
     @property
     def _width(self):
@@ -664,27 +700,16 @@ class GaussianNoiseLikelihood(_ModelLikelihood):
         return device.NoiseTable(self.data, self._sigma2,
                                  log_norm=self.log_norm)
 
-    def _widths(self):
-        return self.n_data, self._width
-
     def _loglike(self, m, w):
         return self._table().loglike(
             m, w, device.NOISE_ROW if self.noise == 'row'
             else device.NOISE_FULL)
 
-    def _check(self, m, w):
-        super()._check(m)
-        if w.ndim != 2 or tuple(w.shape) != (m.shape[0], self._width):
-            raise ValueError('the noise must have shape (%d, %d), not %s' %
-                             (m.shape[0], self._width, tuple(w.shape)))
-
     def from_model(self, m, w):
         """log L of the rows of an (n, P) float64 model output and its noise
         ((n, 3) or (n, P)): cuda tensors in, a cuda tensor out; numpy in,
         numpy out."""
-        if isinstance(m, torch.Tensor) != isinstance(w, torch.Tensor):
-            raise ValueError('the model output and the noise must both be '
-                             'torch tensors or both numpy arrays')
+        self._same_kind(m, w)
         return self._from_outputs(m, w)
 
     def numpy_variance(self, m, w):
@@ -723,7 +748,7 @@ class GaussianNoiseLikelihood(_ModelLikelihood):
         return out
 
 
-class GaussianOutlierLikelihood(_ModelLikelihood):
+class GaussianOutlierLikelihood(_PairLikelihood):
     """Gaussian likelihood of independent measurements some of which are
     outliers -- the two-component mixture per measurement of Hogg, Bovy &
     Lang (2010): a measurement is either good, with the model's mean and
@@ -767,50 +792,26 @@ class GaussianOutlierLikelihood(_ModelLikelihood):
     in (0, +inf), or p_i is outside [0, 1], NaN included.  That changes no bit
     of any other row."""
 
-    _pair = True
-    _what = 'the model output and the mixture'
+    _second = 'mixture'
+    _width = device.OUTLIER_WIDTH
 
     def __init__(self, model, data, sigma=None, *, normalised=True):
         super().__init__(model)
-        data = _bounded_vector(data, 'data', N_NOISE_MAX, 'data points')
-        if not np.all(np.isfinite(data)):
-            raise ValueError('data must be finite')
-        self.data = data.copy()
-        self.n_data = p = len(data)
-        if sigma is None:
-            self.sigma = np.zeros(p)
-        else:
-            self.sigma = _numbers(sigma, p, 'sigma', False).copy()
-        with np.errstate(over='ignore'):
-            self._sigma2 = self.sigma * self.sigma
-        if not np.all(np.isfinite(self._sigma2)):
-            raise ValueError('sigma is too large: sigma^2 is not finite')
-        self.log_norm = -0.5 * p * np.log(2 * np.pi) if normalised else 0.0
+        self._set_data(data, N_NOISE_MAX)
+        self._set_sigma(sigma, normalised)
 
     def _make_table(self):
         return device.NoiseTable(self.data, self._sigma2,
                                  log_norm=self.log_norm)
 
-    def _widths(self):
-        return self.n_data, device.OUTLIER_WIDTH
-
     def _loglike(self, m, w):
         return self._table().outlier_loglike(m, w)
-
-    def _check(self, m, w):
-        super()._check(m)
-        width = device.OUTLIER_WIDTH
-        if w.ndim != 2 or tuple(w.shape) != (m.shape[0], width):
-            raise ValueError('the mixture must have shape (%d, %d), not %s' %
-                             (m.shape[0], width, tuple(w.shape)))
 
     def from_model(self, m, w):
         """log L of the rows of an (n, P) float64 model output and its (n, 6)
         mixture coefficients: cuda tensors in, a cuda tensor out; numpy in,
         numpy out."""
-        if isinstance(m, torch.Tensor) != isinstance(w, torch.Tensor):
-            raise ValueError('the model output and the mixture must both be '
-                             'torch tensors or both numpy arrays')
+        self._same_kind(m, w)
         return self._from_outputs(m, w)
 
     def _parts(self, m, w):
@@ -896,7 +897,7 @@ def gp_correlation(kernel, r):
                      (', '.join(map(repr, GP_KERNELS)), kernel))
 
 
-class GaussianProcessLikelihood(_ModelLikelihood):
+class GaussianProcessLikelihood(_PairLikelihood):
     """Gaussian-process likelihood of P correlated measurements whose full
     covariance depends on the point:
 
@@ -946,8 +947,7 @@ class GaussianProcessLikelihood(_ModelLikelihood):
     of the factorisation outside (0, +inf)).  That changes no bit of any
     other row."""
 
-    _pair = True
-    _what = 'the model output and the covariance input'
+    _second = 'covariance input'
 
     def __init__(self, model, t, data, sigma=None, *, kernel='sqexp',
                  cov='hyper', normalised=True):
@@ -959,11 +959,7 @@ class GaussianProcessLikelihood(_ModelLikelihood):
             raise ValueError('kernel must be one of %s, not %r' %
                              (', '.join(map(repr, GP_KERNELS)), kernel))
         self.kernel = kernel
-        data = _bounded_vector(data, 'data', N_GP_MAX, 'data points')
-        if not np.all(np.isfinite(data)):
-            raise ValueError('data must be finite')
-        self.data = data.copy()
-        self.n_data = p = len(data)
+        p = self._set_data(data, N_GP_MAX)
         if t is None:
             if cov == 'hyper':
                 raise ValueError("cov='hyper' needs the input locations t")
@@ -984,15 +980,7 @@ class GaussianProcessLikelihood(_ModelLikelihood):
             if not np.all(np.isfinite(self.dist)):
                 raise ValueError('t is too spread out: a distance is not '
                                  'finite')
-        if sigma is None:
-            self.sigma = np.zeros(p)
-        else:
-            self.sigma = _numbers(sigma, p, 'sigma', False).copy()
-        with np.errstate(over='ignore'):
-            self._sigma2 = self.sigma * self.sigma
-        if not np.all(np.isfinite(self._sigma2)):
-            raise ValueError('sigma is too large: sigma^2 is not finite')
-        self.log_norm = -0.5 * p * np.log(2 * np.pi) if normalised else 0.0
+        self._set_sigma(sigma, normalised)
 
     @property
     def _width(self):
@@ -1002,20 +990,11 @@ class GaussianProcessLikelihood(_ModelLikelihood):
         return device.GPTable(self.data, self._sigma2, self.dist,
                               kernel=self.kernel, log_norm=self.log_norm)
 
-    def _widths(self):
-        return self.n_data, self._width
-
     def _loglike(self, m, c):
         return self._table().loglike(
             m, c, device.GP_HYPER if self.cov == 'hyper' else device.GP_FULL)
 
-    def _check(self, m, c):
-        super()._check(m)
-        if c.ndim != 2 or tuple(c.shape) != (m.shape[0], self._width):
-            raise ValueError('the covariance input must have shape %s, not %s'
-                             % (self._cov_shape(m.shape[0]), tuple(c.shape)))
-
-    def _cov_shape(self, n):
+    def _second_shape(self, n):
         if self.cov == 'hyper':
             return (n, 3)
         return (n, self.n_data, self.n_data)
@@ -1038,15 +1017,13 @@ class GaussianProcessLikelihood(_ModelLikelihood):
         """log L of the rows of an (n, P) float64 model output and its
         covariance input ((n, 3) or (n, P, P)): cuda tensors in, a cuda
         tensor out; numpy in, numpy out."""
-        if isinstance(m, torch.Tensor) != isinstance(c, torch.Tensor):
-            raise ValueError('the model output and the covariance input must '
-                             'both be torch tensors or both numpy arrays')
+        self._same_kind(m, c)
         if not isinstance(c, torch.Tensor):
             c = np.asarray(c)
         if self.cov == 'full' and (c.ndim != 3 or tuple(c.shape[1:]) !=
                                    (self.n_data, self.n_data)):
             raise ValueError('the covariance input must have shape %s, not %s'
-                             % (self._cov_shape(len(m)), tuple(c.shape)))
+                             % (self._second_shape(len(m)), tuple(c.shape)))
         return self._from_outputs(m, self._flat(c))
 
     def numpy_covariance(self, m, c):
@@ -1134,7 +1111,7 @@ def sum_in_order(terms):
     return total
 
 
-class GaussianProcessSeriesLikelihood(_ModelLikelihood):
+class GaussianProcessSeriesLikelihood(_PairLikelihood):
     """Gaussian-process likelihood of an ordered series of P correlated
     measurements, evaluated as a filter in O(P) per point:
 
@@ -1213,8 +1190,7 @@ class GaussianProcessSeriesLikelihood(_ModelLikelihood):
     which one term answers with a NaN row, is unspecified for a sum -- the
     row is NaN or finite, and no other row is touched."""
 
-    _pair = True
-    _what = 'the model output and the hyper-parameters'
+    _second = 'hyper-parameters'
 
     def __init__(self, model, t, data, sigma=None, *, kernel='matern32',
                  normalised=True):
@@ -1252,11 +1228,7 @@ class GaussianProcessSeriesLikelihood(_ModelLikelihood):
                            key=lambda i: GPS_KERNELS.index(terms[i]))
             self._slots = tuple((terms[i], int(first[i])) for i in order)
         self.kernel = kernel
-        data = _bounded_vector(data, 'data', N_GPS_MAX, 'data points')
-        if not np.all(np.isfinite(data)):
-            raise ValueError('data must be finite')
-        self.data = data.copy()
-        self.n_data = p = len(data)
+        p = self._set_data(data, N_GPS_MAX)
         t = np.asarray(t, float)
         if t.shape != (p,):
             raise ValueError('t must have shape (%d,), not %s' % (p, t.shape))
@@ -1271,15 +1243,7 @@ class GaussianProcessSeriesLikelihood(_ModelLikelihood):
             raise ValueError('t is too spread out: a step is not finite')
         self.t = t.copy()
         self._dt = dt
-        if sigma is None:
-            self.sigma = np.zeros(p)
-        else:
-            self.sigma = _numbers(sigma, p, 'sigma', False).copy()
-        with np.errstate(over='ignore'):
-            self._sigma2 = self.sigma * self.sigma
-        if not np.all(np.isfinite(self._sigma2)):
-            raise ValueError('sigma is too large: sigma^2 is not finite')
-        self.log_norm = -0.5 * p * np.log(2 * np.pi) if normalised else 0.0
+        self._set_sigma(sigma, normalised)
 
     @property
     def _width(self):
@@ -1289,23 +1253,11 @@ class GaussianProcessSeriesLikelihood(_ModelLikelihood):
         return device.GPSTable(self.t, self.data, self._sigma2,
                                kernel=self.kernel, log_norm=self.log_norm)
 
-    def _widths(self):
-        return self.n_data, self._width
-
-    def _check(self, m, h):
-        super()._check(m)
-        if h.ndim != 2 or tuple(h.shape) != (m.shape[0], self._width):
-            raise ValueError('the hyper-parameters must have shape (%d, %d), '
-                             'not %s' % (m.shape[0], self._width,
-                                         tuple(h.shape)))
-
     def from_model(self, m, h):
         """log L of the rows of an (n, P) float64 model output and its (n, 3)
         or (n, 4) hyper-parameters ((n, W) for a sum of terms): cuda tensors
         in, a cuda tensor out; numpy in, numpy out."""
-        if isinstance(m, torch.Tensor) != isinstance(h, torch.Tensor):
-            raise ValueError('the model output and the hyper-parameters must '
-                             'both be torch tensors or both numpy arrays')
+        self._same_kind(m, h)
         return self._from_outputs(m, h)
 
     @staticmethod

@@ -309,6 +309,19 @@ def test_native_shuffle_streams_equal_numpy():
                 assert np.array_equal(rows[ep], orders[i]), (rnd, i, ep)
 
 
+def test_stream_launch_shape():
+    """The (L, R, U) of the row-streaming likelihood kernels on either side of
+    P = 32 and P = 512 (nb_launch.h, ``nb_stream_dispatch``), under all three
+    names."""
+    from nautilus_amd import device
+    for p, shape in ((1, (16, 4, 1)), (32, (16, 4, 1)), (33, (16, 2, 2)),
+                     (512, (16, 2, 2)), (513, (64, 1, 4)),
+                     (1 << 20, (64, 1, 4))):
+        assert device.stream_launch_shape(p) == shape
+    assert device.noise_launch_shape is device.stream_launch_shape
+    assert device.outlier_launch_shape is device.stream_launch_shape
+
+
 def test_amortised_host_append_equals_np_append():
     """``sampler._grow`` (the shells' log L on the host grow batch by batch,
     sampler.py:1135-1136): the same values as ``np.append`` whatever happens
