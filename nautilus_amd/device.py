@@ -225,6 +225,32 @@ class DeviceBound:
                                              _ptr(out), _stream()))
         return out[:, 0], out[:, 1]
 
+    def neural_score_rows(self, x, idx=None, m=0, recentre=False):
+        """(r2, score) of neural bound ``m`` for the rows ``idx`` of ``x``
+        (all rows in order without ``idx``) -- ``nb_neural_score_rows``.
+        ``recentre``: the rows are in the sampler's frame and the bound's
+        periodic shift is applied first, as ``contains`` does.  An index
+        outside ``x`` is refused here, with one host read of the list's
+        extremes: the kernel does not look at it again."""
+        x = as_device_points(x, self.n_dim)
+        n = x.shape[0]
+        if idx is not None:
+            idx = torch.as_tensor(idx).to(
+                device='cuda', dtype=torch.int64).reshape(-1).contiguous()
+            n = idx.shape[0]
+            if n > 0:
+                lo, hi = (int(v) for v in torch.aminmax(idx))
+                if lo < 0 or hi >= x.shape[0]:
+                    raise ValueError(
+                        'row indices %d .. %d outside the %d rows of x' %
+                        (lo, hi, x.shape[0]))
+        out = torch.empty((n, 2), dtype=torch.float64, device='cuda')
+        # (n = 0: the C side checks m and returns without a launch)
+        _lib.check(self._lib.nb_neural_score_rows(
+            self._h, int(m), 1 if recentre else 0, _ptr(x),
+            None if idx is None else _ptr(idx), n, _ptr(out), _stream()))
+        return out[:, 0], out[:, 1]
+
     def propose(self, seed, offset, n, reuse=False):
         x = _buffer('propose', (n, self.n_dim), torch.float64, reuse)
         _lib.check(self._lib.nb_propose(self._h, seed, offset, n, _ptr(x),
@@ -1335,6 +1361,8 @@ def _timed(name):
 DeviceBound.contains = _timed('bound_eval')(DeviceBound.contains)
 DeviceBound.accept = _timed('bound_eval')(DeviceBound.accept)
 DeviceBound.neural_score = _timed('bound_eval')(DeviceBound.neural_score)
+DeviceBound.neural_score_rows = _timed('bound_eval')(
+    DeviceBound.neural_score_rows)
 DeviceBound.propose = _timed('nb_draw_kernel')(DeviceBound.propose)
 DeviceBound.contains_stream = _timed('nb_ell_stream_kernel')(
     DeviceBound.contains_stream)
