@@ -578,39 +578,6 @@ nb_cand_compact_kernel(const int* __restrict__ counts,
   }
 }
 
-template <int DT, int T, int OCC, bool SAMPLE, bool SMALL>
-void launch_cand_m(const CandArgs& a, hipStream_t stream) {
-  const size_t lds = (size_t)a.n_groups * CD_WPB * sizeof(int);
-  const int blocks = (a.n_waves + CD_WPB - 1) / CD_WPB;
-  const int rows_y =
-      !SAMPLE && a.b_chunk > 0 ? (a.nb + a.b_chunk - 1) / a.b_chunk : 1;
-  hipLaunchKernelGGL((nb_cand_kernel<DT, T, OCC, SAMPLE, SMALL>),
-                     dim3((unsigned)blocks, (unsigned)rows_y),
-                     dim3(64 * CD_WPB), lds, stream, a);
-}
-
-// T_S / T_L: tiles per wavefront for proposals / lists (cand_tiles); `small`:
-// the last row tile has at most four real rows (StepTable)
-// OCC_S / OCC_L: wavefronts per SIMD (the register budget) for proposals /
-// lists -- cand_occ() below is the host's copy of the table
-template <int DT, int T_S, int T_L, int OCC_S, int OCC_L>
-int launch_cand_t(const CandArgs& a, bool small, hipStream_t stream) {
-  if (DT > 1 && small) {
-    if (a.mode == CM_SAMPLE)
-      launch_cand_m<DT, T_S, OCC_S, true, (DT > 1)>(a, stream);
-    else
-      launch_cand_m<DT, T_L, OCC_L, false, (DT > 1)>(a, stream);
-  } else {
-    if (a.mode == CM_SAMPLE)
-      launch_cand_m<DT, T_S, OCC_S, true, false>(a, stream);
-    else
-      launch_cand_m<DT, T_L, OCC_L, false, false>(a, stream);
-  }
-  return NB_OK;
-}
-
-}  // namespace
-
 // Tiles per wavefront: two share every A operand.  Proposals: two at any
 // n_dim; lists (first-hit bookkeeping, sphere pre-test, periodic shift next to
 // the points): two up to n_dim 80, one beyond -- the shapes that need no
@@ -619,30 +586,61 @@ int launch_cand_t(const CandArgs& a, bool small, hipStream_t stream) {
 // loop-invariant slot offsets and padding predicates across the bound loop
 // and spilled with two tiles beyond n_dim 64; with the lane group opaque per
 // bound they are recomputed where they are used.
-static int cand_tiles(int dt, int mode) {
-  if (mode == CM_SAMPLE) return 2;
-  return dt <= 5 ? 2 : 1;
+constexpr int cand_tiles(int dt, bool sample) {
+  return sample || dt <= 5 ? 2 : 1;
 }
+
+// wavefronts per SIMD the kernel's registers allow: proposals at 49..64
+// dimensions run three per SIMD (165 registers with six k-steps of operands
+// in flight; 2.41 -> 2.39 ms per 2^20 proposals at n_dim 50, K = M = 4), lists
+// keep two (three would spill)
+constexpr int cand_occ(int dt, bool sample) {
+  if (dt == 1) return 4;
+  if (dt == 2) return 3;
+  return (dt == 4 && sample) ? 3 : 2;
+}
+
+template <int DT, bool SAMPLE, bool SMALL>
+void launch_cand_m(const CandArgs& a, hipStream_t stream) {
+  const size_t lds = (size_t)a.n_groups * CD_WPB * sizeof(int);
+  const int blocks = (a.n_waves + CD_WPB - 1) / CD_WPB;
+  const int rows_y =
+      !SAMPLE && a.b_chunk > 0 ? (a.nb + a.b_chunk - 1) / a.b_chunk : 1;
+  hipLaunchKernelGGL((nb_cand_kernel<DT, cand_tiles(DT, SAMPLE),
+                                     cand_occ(DT, SAMPLE), SAMPLE, SMALL>),
+                     dim3((unsigned)blocks, (unsigned)rows_y),
+                     dim3(64 * CD_WPB), lds, stream, a);
+}
+
+// `small`: the last row tile has at most four real rows (StepTable); bounds
+// of one tile have no such variant
+template <int DT>
+int launch_cand_t(const CandArgs& a, bool small, hipStream_t stream) {
+  if (DT > 1 && small) {
+    if (a.mode == CM_SAMPLE)
+      launch_cand_m<DT, true, (DT > 1)>(a, stream);
+    else
+      launch_cand_m<DT, false, (DT > 1)>(a, stream);
+  } else {
+    if (a.mode == CM_SAMPLE)
+      launch_cand_m<DT, true, false>(a, stream);
+    else
+      launch_cand_m<DT, false, false>(a, stream);
+  }
+  return NB_OK;
+}
+
+}  // namespace
 
 // Geometry of the candidate lists for n points: points per wavefront, number
 // of wavefronts, padded list length (all multiples the kernels rely on).
-// wavefronts per SIMD the kernel's registers allow (the OCC template argument
-// of the launch below): proposals at 49..64 dimensions run three per SIMD (165
-// registers with six k-steps of operands in flight; 2.41 -> 2.39 ms per 2^20
-// proposals at n_dim 50, K = M = 4), lists keep two (three would spill)
-static int cand_occ(int dt, int mode) {
-  if (dt == 1) return 4;
-  if (dt == 2) return 3;
-  return (dt == 4 && mode == CM_SAMPLE) ? 3 : 2;
-}
-
 void nb_cand_shape(int dt, int mode, long long n, int* chunk, int* n_waves,
                    long long* n_pad) {
-  const int tile = 16 * cand_tiles(dt, mode);
+  const int tile = 16 * cand_tiles(dt, mode == CM_SAMPLE);
   // wavefronts of the grid: what the chip holds at once at the kernel's
   // register budget (two per SIMD from n_dim 33 on: 2048; three: 3072), all
   // of CD_MAX_WAVES for the small kernels
-  const int occ = cand_occ(dt, mode);
+  const int occ = cand_occ(dt, mode == CM_SAMPLE);
   const int max_waves = occ >= 3 && dt <= 2 ? CD_MAX_WAVES : 1024 * occ;
   const long long passes = (n + tile - 1) / tile;
   const long long per_wave = (passes + max_waves - 1) / max_waves;
@@ -721,22 +719,9 @@ int nb_launch_cand(int dt, int n_dim, const double* const* blobs_dev,
   int* dense = work + gp;
   a.counts = dense + gp;
   int* totals = a.counts + (long long)n_groups * a.n_waves;
-  int rc = NB_OK;
-  const int live = n_dim - 16 * (dt - 1);        // real rows of the last tile
-  const bool small = live >= 1 && live <= 4;
-  switch (dt) {
-    case 1: rc = launch_cand_t<1, 2, 2, 4, 4>(a, small, stream); break;
-    case 2: rc = launch_cand_t<2, 2, 2, 3, 3>(a, small, stream); break;
-    case 3: rc = launch_cand_t<3, 2, 2, 2, 2>(a, small, stream); break;
-    case 4: rc = launch_cand_t<4, 2, 2, 3, 2>(a, small, stream); break;
-    case 5: rc = launch_cand_t<5, 2, 2, 2, 2>(a, small, stream); break;
-    case 6: rc = launch_cand_t<6, 2, 1, 2, 2>(a, small, stream); break;
-    case 7: rc = launch_cand_t<7, 2, 1, 2, 2>(a, small, stream); break;
-    case 8: rc = launch_cand_t<8, 2, 1, 2, 2>(a, small, stream); break;
-    default:
-      nb_set_error("n_dim > 128 is not supported by the device kernels");
-      return NB_ERR_UNSUPPORTED;
-  }
+  const bool small = nb_tail_of(n_dim).small;
+  const int rc = nb_tile_dispatch(
+      dt, [&](auto t) { return launch_cand_t<t()>(a, small, stream); });
   if (rc != NB_OK) return rc;
   NB_HIP_CHECK(hipGetLastError());
   if (n_groups > 0) {

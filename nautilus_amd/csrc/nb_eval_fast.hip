@@ -634,18 +634,8 @@ template <int DT, int KT1, bool BATCH>
 int launch_fast_impl(const FastArgs& a, hipStream_t stream) {
   const size_t lds = (size_t)2 * FAST_REGION * sizeof(double) +
                      (BATCH ? (FAST_MAX_GROUPS + 1) * sizeof(int) : 0);
-  static bool configured = false;
-  if (!configured) {
-    const hipError_t e = hipFuncSetAttribute(
-        (const void*)nb_eval_fast_kernel<DT, KT1, BATCH>,
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      nb_set_error("hipFuncSetAttribute(%zu bytes LDS) failed: %s", lds,
-                   hipGetErrorString(e));
-      return NB_ERR_HIP;
-    }
-    configured = true;
-  }
+  if (const int rc = nb_allow_lds<nb_eval_fast_kernel<DT, KT1, BATCH>>(lds))
+    return rc;
   // BATCH: the number of passes is only known on the device; workgroups
   // without a pass leave at once
   const long long n_super = (a.n + 127) / 128;
@@ -673,29 +663,13 @@ bool nb_eval_fast_eligible(int n_dim, int K, int M, int E, bool sample) {
 }
 
 static int dispatch_fast(const FastArgs& a, int n_dim, hipStream_t stream) {
-  const int dt = (n_dim + 15) / 16, kt1 = (n_dim + 1 + 15) / 16;
-  int rc = NB_ERR_UNSUPPORTED;
-  switch (4 * dt + (kt1 - dt)) {
-    case 4: rc = launch_fast<1, 1>(a, stream); break;
-    case 5: rc = launch_fast<1, 2>(a, stream); break;
-    case 8: rc = launch_fast<2, 2>(a, stream); break;
-    case 9: rc = launch_fast<2, 3>(a, stream); break;
-    case 12: rc = launch_fast<3, 3>(a, stream); break;
-    case 13: rc = launch_fast<3, 4>(a, stream); break;
-    case 16: rc = launch_fast<4, 4>(a, stream); break;
-    case 17: rc = launch_fast<4, 5>(a, stream); break;
-    case 20: rc = launch_fast<5, 5>(a, stream); break;
-    case 21: rc = launch_fast<5, 6>(a, stream); break;
-    case 24: rc = launch_fast<6, 6>(a, stream); break;
-    case 25: rc = launch_fast<6, 7>(a, stream); break;
-    case 28: rc = launch_fast<7, 7>(a, stream); break;
-    case 29: rc = launch_fast<7, 8>(a, stream); break;
-    case 32: rc = launch_fast<8, 8>(a, stream); break;
-    case 33: rc = launch_fast<8, 9>(a, stream); break;
-    default:
-      nb_set_error("nb_launch_eval_fast: n_dim=%d not eligible", n_dim);
-      return NB_ERR_UNSUPPORTED;
-  }
+  // layer 1 reads (x, 1): one k-tile more where n_dim fills its last tile
+  const int kt1 = (n_dim + 1 + 15) / 16;
+  const int rc = nb_tile_dispatch((n_dim + 15) / 16, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    return kt1 == DT ? launch_fast<DT, DT>(a, stream)
+                     : launch_fast<DT, DT + 1>(a, stream);
+  });
   if (rc != NB_OK) return rc;
   NB_HIP_CHECK(hipGetLastError());
   return NB_OK;

@@ -108,18 +108,7 @@ template <int DT>
 int launch_geom(const GeomArgs& a, hipStream_t stream) {
   constexpr int TPW = DT <= 4 ? 2 : 1, NW = DT <= 4 ? 4 : 8;
   constexpr size_t lds = nb_ell_block_size(DT) * sizeof(double);
-  static bool configured = false;
-  if (lds > 64 * 1024 && !configured) {
-    const hipError_t e = hipFuncSetAttribute(
-        (const void*)nb_geom_kernel<DT, TPW, NW>,
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      nb_set_error("hipFuncSetAttribute(%zu bytes LDS) failed: %s", lds,
-                   hipGetErrorString(e));
-      return NB_ERR_HIP;
-    }
-    configured = true;
-  }
+  if (const int rc = nb_allow_lds<nb_geom_kernel<DT, TPW, NW>>(lds)) return rc;
   const long long n_super = (a.n + 16 * NW * TPW - 1) / (16 * NW * TPW);
   // one workgroup per CU, striding over the 128-row passes
   const long long blocks = n_super < 256 ? n_super : 256;
@@ -138,20 +127,8 @@ int nb_launch_geom(const double* blob_dev, int dt, int count, const double* x,
   a.blob = (const nb_gd*)blob_dev; a.count = count; a.x = (const nb_gd*)x;
   a.n = n; a.out_f64 = out_f64; a.out_u8 = out_u8;
   a.counters = nb_eval_counters();
-  int rc = NB_OK;
-  switch (dt) {
-    case 1: rc = launch_geom<1>(a, stream); break;
-    case 2: rc = launch_geom<2>(a, stream); break;
-    case 3: rc = launch_geom<3>(a, stream); break;
-    case 4: rc = launch_geom<4>(a, stream); break;
-    case 5: rc = launch_geom<5>(a, stream); break;
-    case 6: rc = launch_geom<6>(a, stream); break;
-    case 7: rc = launch_geom<7>(a, stream); break;
-    case 8: rc = launch_geom<8>(a, stream); break;
-    default:
-      nb_set_error("n_dim > 128 is not supported by the device kernels");
-      return NB_ERR_UNSUPPORTED;
-  }
+  const int rc = nb_tile_dispatch(
+      dt, [&](auto t) { return launch_geom<t()>(a, stream); });
   if (rc != NB_OK) return rc;
   NB_HIP_CHECK(hipGetLastError());
   return NB_OK;

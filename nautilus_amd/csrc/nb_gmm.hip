@@ -33,6 +33,7 @@
 // the restart.  Everything is deterministic (fixed reduction orders, Philox
 // for the seeding).
 #include "nb_sym.h"
+#include "nb_launch.h"
 #include "../../include/nautilus_hip.h"
 
 #include <atomic>
@@ -796,18 +797,7 @@ inline int gm_wgs(long long n, int n_init) {
 template <int DT>
 int launch_gmm(const GmmArgs& a, int wgs, hipStream_t stream) {
   const size_t lds = gm_lds_doubles(DT) * sizeof(double);
-  static size_t allowed = 0;
-  if (lds > allowed) {
-    const hipError_t e = hipFuncSetAttribute(
-        (const void*)nb_gmm_kernel<DT>,
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      nb_set_error("hipFuncSetAttribute(%zu bytes LDS) failed: %s", lds,
-                   hipGetErrorString(e));
-      return NB_ERR_HIP;
-    }
-    allowed = lds;
-  }
+  if (const int rc = nb_allow_lds<nb_gmm_kernel<DT>>(lds)) return rc;
   (void)hipGetLastError();
   hipLaunchKernelGGL(nb_gmm_kernel<DT>, dim3(wgs, a.n_init), dim3(GM_THREADS),
                      lds, stream, a);
@@ -860,18 +850,9 @@ int nb_gmm_fit(const double* x, int64_t n, int32_t d, int32_t n_init,
                               (size_t)n_init * GM_SYNC_INTS * sizeof(int),
                               stream));
   const int wgs = gm_wgs(n, n_init);
-  int rc = NB_OK;
-  switch (gm_dt(d)) {
-    case 1: rc = launch_gmm<1>(a, wgs, stream); break;
-    case 2: rc = launch_gmm<2>(a, wgs, stream); break;
-    case 3: rc = launch_gmm<3>(a, wgs, stream); break;
-    case 4: rc = launch_gmm<4>(a, wgs, stream); break;
-    case 5: rc = launch_gmm<5>(a, wgs, stream); break;
-    case 6: rc = launch_gmm<6>(a, wgs, stream); break;
-    case 7: rc = launch_gmm<7>(a, wgs, stream); break;
-    case 8: rc = launch_gmm<8>(a, wgs, stream); break;
-    default: rc = launch_gmm<9>(a, wgs, stream); break;
-  }
+  // (1 <= d <= 128, checked above: gm_dt(d) is 1..9)
+  const int rc = nb_tile_dispatch<NB_MAX_AUG_DT>(
+      gm_dt(d), [&](auto t) { return launch_gmm<t()>(a, wgs, stream); });
   if (rc != NB_OK) return rc;
   NB_HIP_CHECK(hipGetLastError());
   return NB_OK;

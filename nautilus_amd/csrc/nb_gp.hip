@@ -316,20 +316,7 @@ int launch(const double* tab, int n_data, int kernel, const double* model,
            long long ld, const double* cov, long long ld_cov, long long n,
            double log_norm, double* out, hipStream_t stream) {
   const size_t lds = nb_gp_lds_doubles(T) * sizeof(double);
-  if (lds > 65536) {
-    static bool allowed = false;
-    if (!allowed) {
-      const hipError_t e = hipFuncSetAttribute(
-          (const void*)nb_gp_kernel<T, MODE>,
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) {
-        nb_set_error("hipFuncSetAttribute(%zu bytes LDS) failed: %s", lds,
-                     hipGetErrorString(e));
-        return NB_ERR_HIP;
-      }
-      allowed = true;
-    }
-  }
+  if (const int rc = nb_allow_lds<nb_gp_kernel<T, MODE>>(lds)) return rc;
   const long long b = n < (1ll << 20) ? n : (1ll << 20);
   (void)hipGetLastError();
   hipLaunchKernelGGL((nb_gp_kernel<T, MODE>), dim3((unsigned)b),
@@ -344,18 +331,15 @@ int launch_mode(const double* tab, int n_data, int kernel,
                 const double* model, long long ld, const double* cov,
                 long long ld_cov, long long n, double log_norm, double* out,
                 hipStream_t stream) {
-  switch ((n_data + 15) / 16) {
-#define GP_CASE(T)                                                          \
-  case T:                                                                   \
-    return launch<T, MODE>(tab, n_data, kernel, model, ld, cov, ld_cov, n,  \
-                           log_norm, out, stream);
-    GP_CASE(1) GP_CASE(2) GP_CASE(3) GP_CASE(4)
-    GP_CASE(5) GP_CASE(6) GP_CASE(7) GP_CASE(8)
-#undef GP_CASE
+  if (n_data < 1 || n_data > NB_GP_MAX_DATA) {
+    nb_set_error("Gaussian-process likelihood: n_data %d outside 1..%d", n_data,
+                 NB_GP_MAX_DATA);
+    return NB_ERR_ARG;
   }
-  nb_set_error("Gaussian-process likelihood: n_data %d outside 1..%d", n_data,
-               NB_GP_MAX_DATA);
-  return NB_ERR_ARG;
+  return nb_tile_dispatch((n_data + 15) / 16, [&](auto t) {
+    return launch<t(), MODE>(tab, n_data, kernel, model, ld, cov, ld_cov, n,
+                             log_norm, out, stream);
+  });
 }
 
 }  // namespace

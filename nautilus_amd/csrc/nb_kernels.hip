@@ -520,20 +520,13 @@ int nb_launch_draw(const double* blob_dev, int n_dim, unsigned long long seed,
   if (n <= 0) return NB_OK;
   const long long blocks = (n + 63) / 64;
   const size_t lds = (size_t)n_dim * 65 * sizeof(double);
-#define NB_DRAW_CASE(D_T)                                                     \
-  case D_T:                                                                  \
-    hipLaunchKernelGGL(nb_draw_kernel<D_T>, dim3((unsigned)blocks),          \
-                       dim3(64 * DW), lds, stream, blob_dev, seed, offset, n, \
-                       x_out);                                               \
-    break;
-  switch ((n_dim + 15) / 16) {
-    NB_DRAW_CASE(1) NB_DRAW_CASE(2) NB_DRAW_CASE(3) NB_DRAW_CASE(4)
-    NB_DRAW_CASE(5) NB_DRAW_CASE(6) NB_DRAW_CASE(7) NB_DRAW_CASE(8)
-    default:
-      nb_set_error("n_dim > 128 is not supported by the device kernels");
-      return NB_ERR_UNSUPPORTED;
-  }
-#undef NB_DRAW_CASE
+  const int rc = nb_tile_dispatch((n_dim + 15) / 16, [&](auto dt) {
+    hipLaunchKernelGGL(nb_draw_kernel<dt()>, dim3((unsigned)blocks),
+                       dim3(64 * DW), lds, stream, blob_dev, seed, offset, n,
+                       x_out);
+    return NB_OK;
+  });
+  if (rc != NB_OK) return rc;
   NB_HIP_CHECK(hipGetLastError());
   return NB_OK;
 }

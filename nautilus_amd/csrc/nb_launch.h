@@ -5,6 +5,28 @@
 #pragma once
 
 #include "nb_common.h"
+#include "nb_dispatch.h"
+
+// Let Kernel be launched with `bytes` of dynamic LDS (more than 64 KiB needs
+// the opt-in): one call of the runtime whenever a launch asks for more than
+// this kernel was granted before.  What was granted is remembered per process,
+// not per device.
+template <auto Kernel>
+int nb_allow_lds(size_t bytes) {
+  static size_t allowed = 0;
+  if (bytes > allowed) {
+    const hipError_t e = hipFuncSetAttribute(
+        (const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+        (int)bytes);
+    if (e != hipSuccess) {
+      nb_set_error("hipFuncSetAttribute(%zu bytes LDS) failed: %s", bytes,
+                   hipGetErrorString(e));
+      return NB_ERR_HIP;
+    }
+    allowed = bytes;
+  }
+  return NB_OK;
+}
 
 // The launch shape of the row-streaming kernels (nb_poisson_kernel,
 // nb_rowprod_kernel): L lanes share a row, a lane group walks R rows and U

@@ -268,19 +268,8 @@ int launch_variant(const double* blob, int n_dim, int n_comp, const double* x,
     return NB_OK;
   }
   const size_t lds = (size_t)n_comp * record;
-  auto kernel = nb_mixture_resident_kernel<DT, TPW, KL, SMALL>;
-  static size_t allowed = 0;
-  if (lds > allowed) {
-    const hipError_t e = hipFuncSetAttribute(
-        (const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-        (int)lds);
-    if (e != hipSuccess) {
-      nb_set_error("hipFuncSetAttribute(%zu bytes LDS) failed: %s", lds,
-                   hipGetErrorString(e));
-      return NB_ERR_HIP;
-    }
-    allowed = lds;
-  }
+  constexpr auto kernel = nb_mixture_resident_kernel<DT, TPW, KL, SMALL>;
+  if (const int rc = nb_allow_lds<kernel>(lds)) return rc;
   // as many workgroups as the LDS lets a CU hold (at most two by registers),
   // on 256 CUs
   const long long per_cu = MX_LDS_BYTES / lds < 2 ? 1 : 2;
@@ -289,21 +278,6 @@ int launch_variant(const double* blob, int n_dim, int n_comp, const double* x,
                      stream, blob, n_dim, n_comp, x, n, out, label);
   NB_HIP_CHECK(hipGetLastError());
   return NB_OK;
-}
-
-template <int DT>
-int launch(const double* blob, int n_dim, int n_comp, const double* x,
-           long long n, double* out, int* label, hipStream_t stream) {
-  const int kl = 2 * ((n_dim + 7) >> 3);
-  const int rem = n_dim & 15;
-  if (kl == 4 * DT)
-    return launch_variant<DT, 4 * DT, false>(blob, n_dim, n_comp, x, n, out,
-                                             label, stream);
-  if (rem >= 1 && rem <= 4)
-    return launch_variant<DT, 4 * DT - 2, true>(blob, n_dim, n_comp, x, n, out,
-                                                label, stream);
-  return launch_variant<DT, 4 * DT - 2, false>(blob, n_dim, n_comp, x, n, out,
-                                               label, stream);
 }
 
 }  // namespace
@@ -316,16 +290,8 @@ int nb_launch_mixture(const double* blob, int n_dim, int n_comp,
                       const double* x, long long n, double* out, int* label,
                       hipStream_t stream) {
   if (n <= 0) return NB_OK;
-  switch ((n_dim + 15) / 16) {
-    case 1: return launch<1>(blob, n_dim, n_comp, x, n, out, label, stream);
-    case 2: return launch<2>(blob, n_dim, n_comp, x, n, out, label, stream);
-    case 3: return launch<3>(blob, n_dim, n_comp, x, n, out, label, stream);
-    case 4: return launch<4>(blob, n_dim, n_comp, x, n, out, label, stream);
-    case 5: return launch<5>(blob, n_dim, n_comp, x, n, out, label, stream);
-    case 6: return launch<6>(blob, n_dim, n_comp, x, n, out, label, stream);
-    case 7: return launch<7>(blob, n_dim, n_comp, x, n, out, label, stream);
-    case 8: return launch<8>(blob, n_dim, n_comp, x, n, out, label, stream);
-  }
-  nb_set_error("n_dim > 128 unsupported");
-  return NB_ERR_UNSUPPORTED;
+  return nb_row_dispatch(n_dim, [&](auto dt, auto kl, auto small) {
+    return launch_variant<dt(), kl(), small()>(blob, n_dim, n_comp, x, n, out,
+                                               label, stream);
+  });
 }

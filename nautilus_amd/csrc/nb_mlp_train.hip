@@ -49,6 +49,7 @@
 // contracts the row tiles of the minibatch in chunks of G_PAIRS per wavefront
 // (same fixed order of summation, no atomics).
 #include "nb_common.h"
+#include "nb_dispatch.h"
 #include "nb_train_plan.h"
 #include "../../include/nautilus_hip.h"
 
@@ -2149,24 +2150,6 @@ static int chunk_status(const nb_trainer* t, const int* sync,
   return NB_OK;
 }
 
-// launches KERNEL<kt1, large> (kt1 1-9); false: there is none for this kt1
-#define NB_LAUNCH_CASE(KERNEL, KT1_, ...)                                  \
-  case KT1_:                                                               \
-    if (large_) hipLaunchKernelGGL((KERNEL<KT1_, true>), __VA_ARGS__);     \
-    else hipLaunchKernelGGL((KERNEL<KT1_, false>), __VA_ARGS__);           \
-    return true;
-#define NB_LAUNCH_KT1_LARGE(KERNEL, kt1, large, ...)                       \
-  [&, large_ = (large)]() {                                                \
-    switch (kt1) {                                                         \
-      NB_LAUNCH_CASE(KERNEL, 1, __VA_ARGS__) NB_LAUNCH_CASE(KERNEL, 2, __VA_ARGS__) \
-      NB_LAUNCH_CASE(KERNEL, 3, __VA_ARGS__) NB_LAUNCH_CASE(KERNEL, 4, __VA_ARGS__) \
-      NB_LAUNCH_CASE(KERNEL, 5, __VA_ARGS__) NB_LAUNCH_CASE(KERNEL, 6, __VA_ARGS__) \
-      NB_LAUNCH_CASE(KERNEL, 7, __VA_ARGS__) NB_LAUNCH_CASE(KERNEL, 8, __VA_ARGS__) \
-      NB_LAUNCH_CASE(KERNEL, 9, __VA_ARGS__)                               \
-    }                                                                      \
-    return false;                                                          \
-  }()
-
 extern "C" {
 
 int nb_trainer_create(int32_t n_dim, int32_t n_networks, int64_t n_rows,
@@ -2348,11 +2331,16 @@ int nb_trainer_run_fleet(nb_trainer* t, const int32_t* const* perm_dev_of,
     // 32 workgroups per XCD: all of them for its network, or 16 for each of
     // its two
     const dim3 grid(XCD_COUNT * XCD_SLOTS), blk(256);
-    if (!NB_LAUNCH_KT1_LARGE(nb_train_xcd_kernel, t->kt1, t->large, grid, blk,
-                             0, s, a, fleet, t->xcd_map, tab, t->sync_dev)) {
-      nb_set_error("n_dim unsupported");
-      return NB_ERR_UNSUPPORTED;
-    }
+    const int rc = nb_tile_dispatch<NB_MAX_AUG_DT>(t->kt1, [&](auto kt1) {
+      if (t->large)
+        hipLaunchKernelGGL((nb_train_xcd_kernel<kt1(), true>), grid, blk, 0, s,
+                           a, fleet, t->xcd_map, tab, t->sync_dev);
+      else
+        hipLaunchKernelGGL((nb_train_xcd_kernel<kt1(), false>), grid, blk, 0, s,
+                           a, fleet, t->xcd_map, tab, t->sync_dev);
+      return NB_OK;
+    });
+    if (rc != NB_OK) return rc;
     t->t_adam += (long long)n_epochs * steps_per_epoch;
     NB_HIP_CHECK(hipGetLastError());
     if (status_host != nullptr)
@@ -2375,11 +2363,16 @@ int nb_trainer_run_fleet(nb_trainer* t, const int32_t* const* perm_dev_of,
       const dim3 gfb(t->large ? (nb + 15) / 16 : G_ROWT, t->E),
           gg(t->n_jobs, t->E), blk(256);
       t->t_adam += 1;
-      if (!NB_LAUNCH_KT1_LARGE(nb_train_fb_kernel, t->kt1, t->large, gfb, blk,
-                               0, s, a, ep, start, nb)) {
-        nb_set_error("n_dim unsupported");
-        return NB_ERR_UNSUPPORTED;
-      }
+      const int rc = nb_tile_dispatch<NB_MAX_AUG_DT>(t->kt1, [&](auto kt1) {
+        if (t->large)
+          hipLaunchKernelGGL((nb_train_fb_kernel<kt1(), true>), gfb, blk, 0, s,
+                             a, ep, start, nb);
+        else
+          hipLaunchKernelGGL((nb_train_fb_kernel<kt1(), false>), gfb, blk, 0, s,
+                             a, ep, start, nb);
+        return NB_OK;
+      });
+      if (rc != NB_OK) return rc;
       if (t->large)
         hipLaunchKernelGGL(nb_train_g_kernel<true>, gg, blk, 0, s, a, nb,
                            t->t_adam);

@@ -792,33 +792,17 @@ inline int mom_pts_per_wg(long long n_max) {
 }
 inline int mom_sg(int dt) { return MV_WAVES / ((dt + 1) / 2); }
 
-template <typename F>
-int set_lds(F* fn, size_t bytes, size_t* allowed) {
-  if (bytes > *allowed) {
-    const hipError_t e = hipFuncSetAttribute(
-        (const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) {
-      nb_set_error("hipFuncSetAttribute(%zu bytes LDS) failed: %s", bytes,
-                   hipGetErrorString(e));
-      return NB_ERR_HIP;
-    }
-    *allowed = bytes;
-  }
-  return NB_OK;
-}
-
 template <int DT, int NSC>
 int launch_sweep(const MvBatch& b, int nb, int wmax, int d, int n_batch,
                  int call, int n_calls, int mode, int ppw_max,
                  hipStream_t stream) {
-  static size_t allowed = 0;
   const size_t bytes = (size_t)mv_layout(DT, NSC, ppw_max).total * sizeof(double);
   if (bytes > 160 * 1024) {
     nb_set_error("device MVEE: %zu bytes of LDS needed (n_batch too large for "
                  "this n_dim)", bytes);
     return NB_ERR_UNSUPPORTED;
   }
-  const int rc = set_lds(nb_mvee_sweep_kernel<DT, NSC>, bytes, &allowed);
+  const int rc = nb_allow_lds<nb_mvee_sweep_kernel<DT, NSC>>(bytes);
   if (rc != NB_OK) return rc;
   const bool last = mode == 0 && call > 0 && call == n_calls - 1;
   hipLaunchKernelGGL((nb_mvee_sweep_kernel<DT, NSC>), dim3(last ? 1 : wmax, nb),
@@ -831,33 +815,19 @@ template <int NSC>
 int dispatch_sweep(int dt, const MvBatch& b, int nb, int wmax, int d,
                    int n_batch, int call, int n_calls, int mode, int ppw_max,
                    hipStream_t stream) {
-  switch (dt) {
-#define NB_CASE(DT_)                                                          \
-    case DT_:                                                                 \
-      return launch_sweep<DT_, NSC>(b, nb, wmax, d, n_batch, call, n_calls,   \
-                                    mode, ppw_max, stream);
-    NB_CASE(1) NB_CASE(2) NB_CASE(3) NB_CASE(4) NB_CASE(5)
-    NB_CASE(6) NB_CASE(7) NB_CASE(8) NB_CASE(9)
-#undef NB_CASE
-  }
-  nb_set_error("device MVEE supports n_dim <= 128");
-  return NB_ERR_UNSUPPORTED;
+  return nb_tile_dispatch<NB_MAX_AUG_DT>(dt, [&](auto t) {
+    return launch_sweep<t(), NSC>(b, nb, wmax, d, n_batch, call, n_calls, mode,
+                                  ppw_max, stream);
+  });
 }
 
 int launch_moments(int dt, const MomBatch& b, int nb, int d, int wg, int ppw,
                    hipStream_t stream) {
-  switch (dt) {
-#define NB_CASE(DT_)                                                          \
-    case DT_:                                                                 \
-      hipLaunchKernelGGL(nb_moments_kernel<DT_>, dim3(wg, nb),                \
-                         dim3(MV_THREADS), 0, stream, b, d, ppw);             \
-      return NB_OK;
-    NB_CASE(1) NB_CASE(2) NB_CASE(3) NB_CASE(4) NB_CASE(5)
-    NB_CASE(6) NB_CASE(7) NB_CASE(8) NB_CASE(9)
-#undef NB_CASE
-  }
-  nb_set_error("device moments support n_dim <= 128");
-  return NB_ERR_UNSUPPORTED;
+  return nb_tile_dispatch<NB_MAX_AUG_DT>(dt, [&](auto t) {
+    hipLaunchKernelGGL(nb_moments_kernel<t()>, dim3(wg, nb), dim3(MV_THREADS),
+                       0, stream, b, d, ppw);
+    return NB_OK;
+  });
 }
 
 inline long long mom_partial_doubles(long long n_max, int dt) {
@@ -986,9 +956,8 @@ static int mvee_batch(int n_problems, const double* const* xs,
     int rc = launch_moments(dt, qb, nb, d, mom_wg, mom_ppw, stream);
     if (rc != NB_OK) return rc;
     {
-      static size_t allowed = 0;
       const size_t bytes = (size_t)m * m * sizeof(double);
-      rc = set_lds(nb_spd_inverse_kernel, bytes, &allowed);
+      rc = nb_allow_lds<nb_spd_inverse_kernel>(bytes);
       if (rc != NB_OK) return rc;
       hipLaunchKernelGGL(nb_spd_inverse_kernel, dim3(1, nb), dim3(MV_THREADS),
                          bytes, stream, qb, d, mom_wg * mom_sg(dt), nt);
@@ -1083,9 +1052,8 @@ static int whiten(const double* x, long long n, int d, double* xw,
   rc = launch_moments(dtm, b, 1, d, wg, ppw, stream);
   if (rc != NB_OK) return rc;
   {
-    static size_t allowed = 0;
     const size_t bytes = (size_t)d * (d + 1) * sizeof(double);
-    rc = set_lds(nb_whiten_factor_kernel, bytes, &allowed);
+    rc = nb_allow_lds<nb_whiten_factor_kernel>(bytes);
     if (rc != NB_OK) return rc;
     hipLaunchKernelGGL(nb_whiten_factor_kernel, dim3(1), dim3(MV_THREADS), bytes,
                        stream, b, d, wg * mom_sg(dtm), dtm * (dtm + 1) / 2, w,

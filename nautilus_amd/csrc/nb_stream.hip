@@ -296,23 +296,6 @@ int launch_variant(const double* cvec, const double* tiles, int n_dim,
   return NB_OK;
 }
 
-template <int DT>
-int launch(const double* cvec, const double* tiles, int n_dim, const double* x,
-           long long n, unsigned char* mask, hipStream_t stream) {
-  const int kl = 2 * ((n_dim + 7) >> 3);
-  const int rem = n_dim & 15;
-  if (kl == 4 * DT)
-    return launch_variant<DT, 4 * DT, false>(cvec, tiles, n_dim, x, n, mask,
-                                             stream);
-  // (beyond 64 dimensions -- one or two tiles per wavefront -- the 4x4x4
-  // tiles pay since the operands are read ahead: stream_quadform_ahead)
-  if (rem >= 1 && rem <= 4)
-    return launch_variant<DT, 4 * DT - 2, true>(cvec, tiles, n_dim, x, n, mask,
-                                                stream);
-  return launch_variant<DT, 4 * DT - 2, false>(cvec, tiles, n_dim, x, n, mask,
-                                               stream);
-}
-
 }  // namespace
 
 // cvec / tiles point into the stream block of the blob (nb_layout.h hdr[18]):
@@ -322,21 +305,10 @@ int nb_launch_ell_stream(const double* cvec, const double* tiles, int n_dim,
                          const double* x, long long n, unsigned char* mask,
                          hipStream_t stream) {
   if (n <= 0) return NB_OK;
-  const int dt = (n_dim + 15) / 16;
-  int rc = NB_OK;
-  switch (dt) {
-    case 1: rc = launch<1>(cvec, tiles, n_dim, x, n, mask, stream); break;
-    case 2: rc = launch<2>(cvec, tiles, n_dim, x, n, mask, stream); break;
-    case 3: rc = launch<3>(cvec, tiles, n_dim, x, n, mask, stream); break;
-    case 4: rc = launch<4>(cvec, tiles, n_dim, x, n, mask, stream); break;
-    case 5: rc = launch<5>(cvec, tiles, n_dim, x, n, mask, stream); break;
-    case 6: rc = launch<6>(cvec, tiles, n_dim, x, n, mask, stream); break;
-    case 7: rc = launch<7>(cvec, tiles, n_dim, x, n, mask, stream); break;
-    case 8: rc = launch<8>(cvec, tiles, n_dim, x, n, mask, stream); break;
-    default:
-      nb_set_error("n_dim > 128 unsupported");
-      return NB_ERR_UNSUPPORTED;
-  }
+  const int rc = nb_row_dispatch(n_dim, [&](auto dt, auto kl, auto small) {
+    return launch_variant<dt(), kl(), small()>(cvec, tiles, n_dim, x, n, mask,
+                                               stream);
+  });
   if (rc != NB_OK) return rc;
   NB_HIP_CHECK(hipGetLastError());
   return NB_OK;

@@ -461,41 +461,27 @@ int nb_launch_prior_table(const double* u, long long n, int d,
   if (n <= 0) return NB_OK;
   const int ls = d | 1;
   const size_t lds = (size_t)PT_ROWS * ls * sizeof(double);
-  typedef void (*kernel_t)(const double*, long long, int, int, const double*,
-                           const unsigned char*, int, const int*,
-                           const double*, double*);
-  static const kernel_t kernels[12] = {
-      nb_prior_table_kernel<false, 0>, nb_prior_table_kernel<false, 1>,
-      nb_prior_table_kernel<false, 2>, nb_prior_table_kernel<false, 3>,
-      nb_prior_table_kernel<false, 4>, nb_prior_table_kernel<false, 5>,
-      nb_prior_table_kernel<true, 0>,  nb_prior_table_kernel<true, 1>,
-      nb_prior_table_kernel<true, 2>,  nb_prior_table_kernel<true, 3>,
-      nb_prior_table_kernel<true, 4>,  nb_prior_table_kernel<true, 5>};
   if (level < 0 || level > 5) {
     nb_set_error("bad prior table level %d", level);
     return NB_ERR_ARG;
   }
-  const int which = 6 * (column_major != 0) + level;
-  static size_t allowed[12] = {};
-  if (lds > allowed[which]) {
-    const hipError_t e = hipFuncSetAttribute(
-        (const void*)kernels[which],
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      nb_set_error("hipFuncSetAttribute(%zu bytes LDS) failed: %s", lds,
-                   hipGetErrorString(e));
-      return NB_ERR_HIP;
-    }
-    allowed[which] = lds;
-  }
   long long blocks = (n + PT_ROWS - 1) / PT_ROWS;
   if (blocks > 2048) blocks = 2048;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(kernels[which], dim3((unsigned)blocks), dim3(PT_THREADS),
-                     lds, stream, u, n, d, ls, par, kind, n_keys, key_column,
-                     key_value, out);
-  NB_HIP_CHECK(hipGetLastError());
-  return NB_OK;
+  auto launch = [&](auto cm) {
+    // the six levels, counted from one
+    return nb_tile_dispatch<6>(level + 1, [&](auto level1) {
+      constexpr auto kernel =
+          nb_prior_table_kernel<decltype(cm)::value, level1() - 1>;
+      if (const int rc = nb_allow_lds<kernel>(lds)) return rc;
+      (void)hipGetLastError();
+      hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(PT_THREADS), lds,
+                         stream, u, n, d, ls, par, kind, n_keys, key_column,
+                         key_value, out);
+      NB_HIP_CHECK(hipGetLastError());
+      return NB_OK;
+    });
+  };
+  return !column_major ? launch(std::false_type()) : launch(std::true_type());
 }
 
 int nb_launch_transform(const double* ell_block, int dt, int n_dim,
@@ -504,19 +490,12 @@ int nb_launch_transform(const double* ell_block, int dt, int n_dim,
   if (n <= 0) return NB_OK;
   long long blocks = ((n + 15) / 16 + 3) / 4;
   if (blocks > 2048) blocks = 2048;
-  switch (dt) {
-#define NB_CASE(DT_)                                                         \
-    case DT_:                                                                \
-      hipLaunchKernelGGL(nb_transform_kernel<DT_>, dim3((unsigned)blocks),   \
-                         dim3(256), 0, stream, ell_block, n_dim, x, n, y);   \
-      break;
-    NB_CASE(1) NB_CASE(2) NB_CASE(3) NB_CASE(4)
-    NB_CASE(5) NB_CASE(6) NB_CASE(7) NB_CASE(8)
-#undef NB_CASE
-    default:
-      nb_set_error("n_dim > 128 is not supported by the device kernels");
-      return NB_ERR_UNSUPPORTED;
-  }
+  const int rc = nb_tile_dispatch(dt, [&](auto t) {
+    hipLaunchKernelGGL(nb_transform_kernel<t()>, dim3((unsigned)blocks),
+                       dim3(256), 0, stream, ell_block, n_dim, x, n, y);
+    return NB_OK;
+  });
+  if (rc != NB_OK) return rc;
   NB_HIP_CHECK(hipGetLastError());
   return NB_OK;
 }

@@ -669,7 +669,9 @@ def mixture_record(dt):
 
 def mixture_launch_shape(n_dim, n_components):
     """(dt, kl, small, tpw, resident, points_per_round) of
-    ``nb_mixture_loglike`` (nb_mixture.hip, ``launch`` / ``launch_variant``):
+    ``nb_mixture_loglike`` (``nb_row_dispatch`` of nb_dispatch.h, which
+    tests/test_dispatch.py holds this against, and ``launch_variant`` of
+    nb_mixture.hip):
     the kernel is instantiated for dt = ceil(n_dim / 16) tiles, ``kl`` k-steps
     that hold real features and ``small`` (the last row tile has at most 4
     real rows, n_dim mod 16 in 1..4); a wavefront owns ``tpw`` tiles of 16

@@ -117,7 +117,8 @@ TWINS = ('f64', 'binv32', 'c32', 'acc32', 'drop')
 
 def stream_variant(d):
     """What nb_stream.hip launches for n_dim = d: (DT, KL, SMALL, parity of
-    the row loads, kernel) -- ``launch`` and ``launch_variant`` restated."""
+    the row loads, kernel) -- ``nb_row_dispatch`` (nb_dispatch.h) and
+    ``launch_variant`` restated."""
     dt, rem = (d + 15) // 16, d & 15
     full = 2 * ((d + 7) >> 3) == 4 * dt
     kernel = 'pipe2' if 2 <= dt <= 4 else 'pipe1' if 5 <= dt <= 7 else 'plain'

@@ -51,8 +51,9 @@ def test_dimension_tables_are_the_suites():
 
 
 def stream_instantiations():
-    """Every (DT, KL, SMALL) nb_stream.hip's ``launch`` can pick, with the
-    kernel ``launch_variant`` starts for it: per tile count the full K range,
+    """Every (DT, KL, SMALL) ``nb_row_dispatch`` can pick, with the kernel
+    nb_stream.hip's ``launch_variant`` starts for it: per tile count the full
+    K range,
     and the range trimmed by two slots with a last row tile of at most four
     rows (SMALL) and without."""
     out = set()
