@@ -57,6 +57,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
@@ -66,8 +67,6 @@ namespace {
 
 typedef double nb_d2 __attribute__((ext_vector_type(2)));
 
-constexpr int LD1 = 112, LD2 = 64, LD3 = 32, LD4 = 16;
-constexpr int SMALL_BATCH = 200;    // largest batch of the compile-time layout
 static_assert(NB_TRAIN_MAX_BATCH % 16 == 0, "row tiles of the largest batch");
 // transposed copies of the weight tiles of layers 2-4 (operands of the
 // backward products): [ht][kt] tiles, element (hh, kk) = W[16 kt + kk][16 ht + hh]
@@ -131,7 +130,6 @@ __device__ __forceinline__ T* uniform_ptr(T* p) {
   return (T*)((unsigned long long)lo | ((unsigned long long)hi << 32));
 }
 
-constexpr int MAX_RESIDENT = 16;   // networks of one resident launch
 struct FleetData { NetData d[MAX_RESIDENT]; };
 
 struct TrainArgs {
@@ -522,13 +520,9 @@ struct FbLds {
 struct StashPtrs {
   nb_gd *A0, *A1, *A2, *A3, *D1, *D2, *D3, *D4;
 };
-// doubles of a stash of `rows` rows (a multiple of 16) ...
-__host__ __device__ constexpr long long stash_doubles(long long rows, int ld0) {
-  return rows * (ld0 + 2 * (LD1 + LD2 + LD3) + LD4);
-}
-// ... of `rows` = MAXB, or 16 * TrainArgs::rowt for the LARGE kernels, which
-// keep the loss partials of the row tiles behind it (the small layout has
-// them in scal[8 ..])
+// the stash (stash_doubles, nb_train_plan.h) has MAXB rows, or 16 *
+// TrainArgs::rowt for the LARGE kernels, which keep the loss partials of the
+// row tiles behind it (the small layout has them in scal[8 ..])
 template <bool LARGE>
 __device__ __forceinline__ int stash_rows(const TrainArgs& a) {
   return LARGE ? 16 * a.rowt : MAXB;
@@ -643,27 +637,16 @@ __device__ __forceinline__ void fb_body(const TrainArgs& a, const NetState& st,
   {
     double in[KS1];
     lds_operand<KS1>(sA0, lane, in);
-#ifdef NB_W1B_BEHIND_INPUT
-    // second tile's operands while the first chain waits for its own
-#pragma unroll
-    for (int i = 0; i < KS1 / 2; ++i)
-      load_pair<NB_HT1>(rW, W1 + ht1b * NB_TILE, lane, -1, i, w1r[1]);
-    __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
     for (int rep = 0; rep < 2; ++rep) {
       const int ht = wave + 4 * rep;
       const bool run = ht < NB_HT1;
-#ifdef NB_W1B_BEHIND_INPUT
-      constexpr int NS = KS1 / 2, H = 0, NW = 2 * NS - H;
-#else
       constexpr int NS = KS1 / 2, H = (NS + 1) / 2, NW = 2 * NS - H;
-#endif
       const nb_d4 acc = mma_l1_hook<KS1>(w1r[rep], in, ks1, run, [&](int p) {
         const int q = rep * NS + p;
         if (q < H) {
 #pragma unroll
-          for (int i = NS * q / (H ? H : 1); i < NS * (q + 1) / (H ? H : 1); ++i)
+          for (int i = NS * q / H; i < NS * (q + 1) / H; ++i)
             load_pair<NB_HT1>(rW, W1 + ht1b * NB_TILE, lane, -1, i, w1r[1]);
         } else {
 #pragma unroll
@@ -1308,17 +1291,12 @@ __global__ void nb_train_epoch_kernel(TrainArgs a, long long t_adam) {
 // (s_waitcnt) and a consumer to drop its CU's L1 (buffer_inv): no L2
 // write-back, and the barrier is one atomic in that L2.
 // ---------------------------------------------------------------------------
-// s_sleep between two polls of a barrier counter, in units of 64 clocks: 16
-// when more than four networks train at once (the polls of eight busy XCDs
-// get into each other's way: 3 us per step), 6 for up to four (half a
-// microsecond less barrier latency per step)
-#ifndef NB_POLL_SLEEP
-#define NB_POLL_SLEEP 2
-#endif
-#ifndef NB_POLL_SLEEP_FEW
-#define NB_POLL_SLEEP_FEW 1
-#endif
-constexpr int XCD_COUNT = 8;
+// s_sleep between two polls of a barrier counter, in units of 64 clocks: 2
+// when more than four networks train at once, 1 for up to four.  (Once 16 --
+// the polls of eight busy XCDs got into each other's way -- and 6; measured
+// again on the later kernel, profiles/r06/train_poll_sleep.txt, the interval
+// is worth ~1 % of a step and the shortest sleeps were adopted.)
+constexpr int NB_POLL_SLEEP = 2, NB_POLL_SLEEP_FEW = 1;
 // per network 512 bytes: [0] counter of the barrier behind FB (and of those
 // around the epochs), [1] error, [32] the count of reported upper stashes,
 // [64] counter of the barrier that ends a step -- the counters of different
@@ -1397,12 +1375,6 @@ __device__ __forceinline__ void xcd_wait_for(int* counter, int* err, int target,
   }
   lds_barrier();
 }
-
-// networks of the XCDs: up to two per XCD (two workgroups per CU), -1 = none
-struct XcdMap {
-  int n_nets;
-  int net[XCD_COUNT][2];
-};
 
 // per network: its barrier record (SYNC_WORDS ints) in the arena
 struct SyncTable { int* rec[MAX_RESIDENT]; };
@@ -1804,25 +1776,15 @@ struct TrainSwitches {
   // NB_TRAIN_NO_SCHEDULE: resident kernel with all G jobs behind the barrier,
   // in rounds [INTEGRATION.md, profiles/r04/second_session/train_slots_*.txt]
   bool no_schedule;
-  // NB_TRAIN_SYNC_SHIFT=k: the trainer's counters 16 KB + k KB into the block
-  // instead of at its start [profiles/tools/train_sync_shift.py]
-  bool sync_shift;
-  long sync_shift_kb;
-  // NB_TRAIN_BLOCK_SHIFT=k: the block starts k KB into its allocation
-  // [profiles/tools/train_block_shift.py, train_sync_shift.py]
-  bool block_shift;
-  long block_shift_kb;
   // NB_TRAIN_LATE_ONLY=n, NB_TRAIN_LATE_SHAPE=s: g_plan's forced values, -1 =
   // the cost model's choice [profiles/tools/train_plan_sweep.py]
   int late_only, late_shape;
   // NB_TRAIN_DEBUG: the schedule and the form taken, on stderr
-  // [tests/test_emulator_hparams_gpu.py]
+  // [tests/test_emulator_hparams_gpu.py].  sync_arena reads it on its own,
+  // once per process (the timings of the arena's places), as it does
+  // NB_TRAIN_SYNC_PLACE=p: place p for the barrier records of every XCD
+  // [INTEGRATION.md]
   bool debug;
-  // NB_TRAIN_DEBUG_BLOCK: the address of the block [profiles/tools/
-  // train_block_shift.py].  sync_arena reads it on its own, once per process
-  // (the timings of the arena's places), as it does NB_TRAIN_SYNC_PLACE=p:
-  // place p for the barrier records of every XCD [INTEGRATION.md]
-  bool debug_block;
 };
 static TrainSwitches train_switches() {
   auto num = [](const char* name, long unset) {
@@ -1832,14 +1794,9 @@ static TrainSwitches train_switches() {
   sw.two_launch = getenv("NB_TRAIN_TWO_LAUNCH") != nullptr;
   sw.no_resident = getenv("NB_TRAIN_NO_RESIDENT") != nullptr;
   sw.no_schedule = getenv("NB_TRAIN_NO_SCHEDULE") != nullptr;
-  sw.sync_shift = getenv("NB_TRAIN_SYNC_SHIFT") != nullptr;
-  sw.sync_shift_kb = num("NB_TRAIN_SYNC_SHIFT", 0);
-  sw.block_shift = getenv("NB_TRAIN_BLOCK_SHIFT") != nullptr;
-  sw.block_shift_kb = num("NB_TRAIN_BLOCK_SHIFT", 0);
   sw.late_only = (int)num("NB_TRAIN_LATE_ONLY", -1);
   sw.late_shape = (int)num("NB_TRAIN_LATE_SHAPE", -1);
   sw.debug = getenv("NB_TRAIN_DEBUG") != nullptr;
-  sw.debug_block = getenv("NB_TRAIN_DEBUG_BLOCK") != nullptr;
   return sw;
 }
 
@@ -1897,7 +1854,7 @@ static bool sync_arena() {
     for (int p = 1; p < ARENA_PLACES; ++p)
       if (host[x * ARENA_PLACES + p] < host[x * ARENA_PLACES + best]) best = p;
     g_place_of_xcd[x] = forced ? atoi(forced) % ARENA_PLACES : best;
-    if (getenv("NB_TRAIN_DEBUG_BLOCK") != nullptr) {
+    if (getenv("NB_TRAIN_DEBUG") != nullptr) {
       fprintf(stderr, "[trainer] XCD %d: ticks per 48 dependent atomics by "
               "place:", x);
       for (int p = 0; p < ARENA_PLACES; ++p)
@@ -1925,7 +1882,6 @@ struct nb_trainer {
   double tol = 0.0, lr = 1e-2, b1 = 0.9, b2 = 0.999, eps = 1e-8;
   long long t_adam = 0;
   char* block = nullptr;           // the one device allocation (alloc_block)
-  char* block_alloc = nullptr;
   int* sync_dev = nullptr;         // per network: counter, error, xcc mask
   int* jobs_dev = nullptr;         // job list of the G phase
   int* sched_dev = nullptr;        // (early, late) job per workgroup, or null
@@ -1985,27 +1941,11 @@ static void print_plan(const TrainPlan& p) {
     }
 }
 
-// ONE allocation for everything the kernels touch -- [barrier counters, 12
-// KB][network records, 1 KB][job lists, 1 + 2 KB][weights, moments, stash, loss
-// curve and scalars of every network] -- so that the small arrays lie the
-// same way relative to each other and to the pool in every process (as
-// separate allocations they landed wherever the allocator had a slot, and
-// the step time followed).
-constexpr size_t OFF_NETS = 12288, OFF_JOBS = 13312, OFF_SCHED = 14336,
-                 OFF_SYNC2 = 16384, OFF_POOL = 32768;
+// the counters and the network records fit their places in the block
+// (nb_train_plan.h)
 static_assert(SYNC_INTS * sizeof(int) <= OFF_NETS &&
               MAX_RESIDENT * sizeof(NetState) <= OFF_JOBS - OFF_NETS,
               "trainer block layout");
-// a network's part of the pool, in doubles: W, M, V, WT, then these
-struct PoolLayout { long long stash, curve, per_net; };
-static PoolLayout pool_layout(const nb_trainer* t) {
-  const long long stash =
-      (long long)MAXB * (16 * t->kt1 + 2 * (LD1 + LD2 + LD3) + LD4);
-  const long long curve = (t->max_iter + 1) & ~1LL;   // 16-byte alignment
-  // (a multiple of 4 KB: no line of one network's record next to another's)
-  return {stash, curve,
-          (3 * t->n_w + WT_DOUBLES + stash + curve + 32 + 511) / 512 * 512};
-}
 
 // allocates the block, points the trainer into it and uploads the job lists
 static int alloc_block(nb_trainer* t, const TrainSwitches& sw,
@@ -2014,31 +1954,16 @@ static int alloc_block(nb_trainer* t, const TrainSwitches& sw,
   // [sched (2 per workgroup)][its job records]
   std::vector<int> sched = plan.sched;
   sched.insert(sched.end(), plan.sched_jobs.begin(), plan.sched_jobs.end());
-  // (with the NB_TRAIN_SYNC_SHIFT experiment the counters sit at OFF_SYNC2,
-  // inside the schedule's slot: the schedule then has to end in front of them)
-  const size_t sched_end = sw.sync_shift ? OFF_SYNC2 : OFF_POOL;
-  if (plan.jobs.size() * sizeof(int) > OFF_SCHED - OFF_JOBS ||
-      sched.size() * sizeof(int) > sched_end - OFF_SCHED) {
+  if (plan.jobs.size() * sizeof(int) > JOBS_SLOT ||
+      sched.size() * sizeof(int) > SCHED_SLOT) {
     nb_set_error("trainer: job lists exceed their slots");
     return NB_ERR_ARG;
   }
-  // (whole 2 MB fragments: the mapping of a block that ends inside one was
-  // seen to cost up to a microsecond per step)
-  const size_t bytes =
-      (OFF_POOL + (size_t)t->per_net * t->E * sizeof(double) +
-       (2u << 20) - 1) / (2u << 20) * (2u << 20);
-  const size_t shift = sw.block_shift ? (size_t)sw.block_shift_kb * 1024 : 0;
-  const size_t slack = sw.block_shift ? (2u << 20) : 0;
-  hipError_t e = hipMalloc((void**)&t->block_alloc, bytes + slack);
-  if (e == hipSuccess) e = hipMemset(t->block_alloc, 0, bytes + slack);
+  const size_t bytes = block_bytes(t->per_net, t->E);
+  hipError_t e = hipMalloc((void**)&t->block, bytes);
+  if (e == hipSuccess) e = hipMemset(t->block, 0, bytes);
   if (e == hipSuccess) {
-    t->block = t->block_alloc + shift;
-    if (sw.debug_block)
-      fprintf(stderr, "[trainer] block at %p\n", (void*)t->block);
     t->sync_dev = (int*)t->block;
-    if (sw.sync_shift)
-      t->sync_dev = (int*)(t->block + OFF_SYNC2 +
-                           (size_t)sw.sync_shift_kb * 1024);
     t->nets_dev = (NetState*)(t->block + OFF_NETS);
     t->jobs_dev = (int*)(t->block + OFF_JOBS);
     t->pool = (double*)(t->block + OFF_POOL);
@@ -2057,37 +1982,16 @@ static int alloc_block(nb_trainer* t, const TrainSwitches& sw,
   return NB_OK;
 }
 
-// A resident network takes one workgroup slot on every CU of an XCD (of two
-// per CU).  Every trainer owns its XCDs exclusively -- two resident kernels
-// that each hold a part of an XCD could wait for each other -- and puts
-// one network on each while they last, two beyond that (16 networks on the
-// 8 XCDs); a trainer that finds too few free XCDs trains with two launches
-// per step instead.
+// the XCDs of the trainer's networks, or two launches per step (plan_xcds)
 static void assign_xcds(nb_trainer* t, const TrainSwitches& sw) {
-  const int n_networks = t->E;
-  t->two_launch = n_networks > MAX_RESIDENT || sw.two_launch ||
-                  sw.no_resident || !xcd_pinning_available();
-  t->xcd_map.n_nets = n_networks;
-  for (int x = 0; x < XCD_COUNT; ++x)
-    t->xcd_map.net[x][0] = t->xcd_map.net[x][1] = -1;
-  if (t->two_launch) return;
-  int n_free = 0;
-  for (int x = 0; x < XCD_COUNT; ++x)
-    if (!(g_xcd_in_use & (1u << x))) ++n_free;
-  if (n_networks > 2 * n_free) {
-    t->two_launch = true;
-    return;
-  }
-  // as many XCDs as there are networks (up to the free ones), the
-  // networks dealt out round-robin
-  const int n_use = n_networks < n_free ? n_networks : n_free;
-  int xs_used[XCD_COUNT], k = 0;
-  for (int x = 0; x < XCD_COUNT && k < n_use; ++x)
-    if (!(g_xcd_in_use & (1u << x))) xs_used[k++] = x;
-  for (int i = 0; i < n_networks; ++i)
-    t->xcd_map.net[xs_used[i % n_use]][i / n_use] = i;
-  for (int j = 0; j < n_use; ++j) t->xcd_owned |= 1u << xs_used[j];
-  g_xcd_in_use |= t->xcd_owned;
+  // (no probe launch where the switches or the count alone decide)
+  const bool allowed = !sw.two_launch && !sw.no_resident &&
+                       t->E <= MAX_RESIDENT && xcd_pinning_available();
+  const XcdPlan p = plan_xcds(t->E, g_xcd_in_use, allowed);
+  t->two_launch = p.two_launch;
+  t->xcd_map = p.map;
+  t->xcd_owned = p.owned;
+  g_xcd_in_use |= p.owned;
 }
 
 // the records of the networks, and their weights in tiles (nb_train_plan.h)
@@ -2098,13 +2002,13 @@ static int upload_networks(nb_trainer* t, const PoolLayout& lay,
   std::vector<double> w, wt;
   for (int i = 0; i < t->E; ++i) {
     NetState s;
-    double* base = t->pool + (size_t)i * lay.per_net;
-    s.W = (nb_gd*)base; s.M = s.W + t->n_w; s.V = s.M + t->n_w;
-    s.WT = s.V + t->n_w;
-    s.stash = s.WT + WT_DOUBLES;
+    nb_gd* base = (nb_gd*)(t->pool + (size_t)i * lay.per_net);
+    s.W = base + lay.W; s.M = base + lay.M; s.V = base + lay.V;
+    s.WT = base + lay.WT;
+    s.stash = base + lay.stash;
     t->pool_stash.push_back(s.stash);
-    s.loss_curve = s.stash + lay.stash;
-    s.scal = s.loss_curve + lay.curve;
+    s.loss_curve = base + lay.curve;
+    s.scal = base + lay.scal;
     t->nets_host.push_back(s);
     pack_network(t->n_dim, t->kt1, coefs + 4 * i, icpts + 4 * i, w, wt);
     e = hipMemcpy((void*)s.W, w.data(), w.size() * sizeof(double),
@@ -2150,6 +2054,95 @@ static int chunk_status(const nb_trainer* t, const int* sync,
   return NB_OK;
 }
 
+// f(std::true_type) for the trainer of a large stash, f(std::false_type)
+// otherwise: the LARGE argument of the kernels
+template <class F>
+static auto with_large(const nb_trainer* t, F&& f) {
+  return t->large ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// ---- a chunk of epochs (a.n_epochs, steps_per_epoch steps each), enqueued ---
+// resident form: one launch
+static int run_resident(nb_trainer* t, const TrainArgs& a,
+                        const int32_t* const* perm_dev_of, int steps_per_epoch,
+                        hipStream_t s) {
+  FleetData fleet;
+  for (int i = 0; i < MAX_RESIDENT; ++i) {
+    const int k = i < t->E ? i : 0;
+    fleet.d[i].X = (const nb_gd*)t->Xs[k];
+    fleet.d[i].y = (const nb_gd*)t->ys[k];
+    fleet.d[i].perm = (const nb_gi*)perm_dev_of[k];
+    fleet.d[i].n = t->ns[k];
+    fleet.d[i].batch = epoch_steps(t->ns[k], t->batch).batch;
+  }
+  NB_HIP_CHECK(hipMemsetAsync(t->sync_dev, 0, SYNC_INTS * sizeof(int), s));
+  SyncTable tab;
+  for (int i = 0; i < MAX_RESIDENT; ++i) tab.rec[i] = t->sync_dev;
+  for (int x = 0; x < XCD_COUNT; ++x)
+    for (int w = 0; w < 2; ++w) {
+      const int net = t->xcd_map.net[x][w];
+      if (net < 0) continue;
+      tab.rec[net] = sync_arena()
+          ? g_arena + g_place_of_xcd[x] * ARENA_PLACE_INTS +
+                (x * 2 + w) * SYNC_WORDS
+          : t->sync_dev + SYNC_WORDS * net;
+      if (tab.rec[net] != t->sync_dev + SYNC_WORDS * net)
+        NB_HIP_CHECK(hipMemsetAsync(tab.rec[net], 0,
+                                    SYNC_WORDS * sizeof(int), s));
+    }
+  // 32 workgroups per XCD: all of them for its network, or 16 for each of
+  // its two
+  const dim3 grid(XCD_COUNT * XCD_SLOTS), blk(256);
+  const int rc = nb_tile_dispatch<NB_MAX_AUG_DT>(t->kt1, [&](auto kt1) {
+    with_large(t, [&](auto large) {
+      hipLaunchKernelGGL((nb_train_xcd_kernel<kt1(), large()>), grid, blk, 0,
+                         s, a, fleet, t->xcd_map, tab, t->sync_dev);
+    });
+    return NB_OK;
+  });
+  if (rc != NB_OK) return rc;
+  t->t_adam += (long long)a.n_epochs * steps_per_epoch;
+  return NB_OK;
+}
+
+// two launches per step: one training set, contiguous shuffles
+static int run_two_launch(nb_trainer* t, const TrainArgs& a,
+                          const int32_t* const* perm_dev_of,
+                          int steps_per_epoch, hipStream_t s) {
+  for (int i = 1; i < t->E; ++i)
+    if (perm_dev_of[i] != perm_dev_of[0] + (size_t)i * a.n_epochs * a.n) {
+      nb_set_error("two-launch training needs the shuffles of all networks "
+                   "in one (E, n_epochs, n) array");
+      return NB_ERR_ARG;
+    }
+  for (int ep = 0; ep < a.n_epochs; ++ep) {
+    for (int sidx = 0; sidx < steps_per_epoch; ++sidx) {
+      const long long start = (long long)sidx * a.batch;
+      const int nb = (int)((a.n - start < a.batch) ? (a.n - start) : a.batch);
+      // (all G_ROWT row tiles: the ones past the end of a short minibatch
+      // clear their delta rows; LARGE: the row tiles of the minibatch)
+      const dim3 gfb(t->large ? (nb + 15) / 16 : G_ROWT, t->E),
+          gg(t->n_jobs, t->E), blk(256);
+      t->t_adam += 1;
+      const int rc = nb_tile_dispatch<NB_MAX_AUG_DT>(t->kt1, [&](auto kt1) {
+        with_large(t, [&](auto large) {
+          hipLaunchKernelGGL((nb_train_fb_kernel<kt1(), large()>), gfb, blk, 0,
+                             s, a, ep, start, nb);
+        });
+        return NB_OK;
+      });
+      if (rc != NB_OK) return rc;
+      with_large(t, [&](auto large) {
+        hipLaunchKernelGGL(nb_train_g_kernel<large()>, gg, blk, 0, s, a, nb,
+                           t->t_adam);
+      });
+    }
+    hipLaunchKernelGGL(nb_train_epoch_kernel, dim3(t->E), dim3(64), 0, s, a,
+                       t->t_adam);
+  }
+  return NB_OK;
+}
+
 extern "C" {
 
 int nb_trainer_create(int32_t n_dim, int32_t n_networks, int64_t n_rows,
@@ -2188,7 +2181,7 @@ int nb_trainer_create_fleet(int32_t n_dim, int32_t n_networks,
       t->shared_set = false;
   }
   t->n_w = (long long)nb_net_tiles(t->kt1) * NB_TILE;
-  const PoolLayout lay = pool_layout(t);
+  const PoolLayout lay = pool_layout(t->kt1, t->n_w, t->max_iter);
   t->per_net = lay.per_net;
   TrainPlan plan;
   plan.jobs = g_jobs_rounds(t->kt1);
@@ -2229,32 +2222,23 @@ int nb_trainer_set_hparams(nb_trainer* t, double lr, double beta1,
                  NB_TRAIN_MAX_BATCH);
     return NB_ERR_UNSUPPORTED;
   }
-  // The layout follows the largest minibatch any network sees (batch clipped
-  // to its rows, as scikit-learn does): up to SMALL_BATCH rows the stash in
-  // the pool (G_ROWT row tiles), beyond it one laid out for the batch, with
-  // the loss partials of its row tiles behind it.  A change of layout waits
-  // for the device (work still queued reads the network records).
-  long long eff = 0;
-  for (long long n : t->ns) eff = std::max(eff, std::min(n, (long long)batch));
-  const bool large = eff > SMALL_BATCH;
-  const int rowt = large ? (int)((eff + 15) / 16) : G_ROWT;
-  // doubles of one network in a large stash of `rt` row tiles
-  auto per_net = [&](int rt) {
-    return (stash_doubles(16LL * rt, 16 * t->kt1) + rt + 511) / 512 * 512;
-  };
+  // The stash in the pool or a large one (stash_choice).  A change of layout
+  // waits for the device (work still queued reads the network records).
+  const auto [large, rowt] = stash_choice(t->ns, batch);
   if (large != t->large || (large && rowt > t->big_rowt)) {
     NB_HIP_CHECK(hipDeviceSynchronize());
     if (large && rowt > t->big_rowt) {
       if (t->big_stash) NB_HIP_CHECK(hipFree(t->big_stash));
       t->big_stash = nullptr;
       t->big_rowt = 0;
-      const size_t bytes = (size_t)per_net(rowt) * t->E * sizeof(double);
+      const size_t bytes =
+          (size_t)large_per_net(rowt, t->kt1) * t->E * sizeof(double);
       NB_HIP_CHECK(hipMalloc((void**)&t->big_stash, bytes));
       // (finite contents: G scales the rows past a minibatch by zero)
       NB_HIP_CHECK(hipMemset(t->big_stash, 0, bytes));
       t->big_rowt = rowt;
     }
-    const long long per = per_net(t->big_rowt);
+    const long long per = large_per_net(t->big_rowt, t->kt1);
     for (int i = 0; i < t->E; ++i)
       t->nets_host[i].stash = large ? (nb_gd*)(t->big_stash + (size_t)i * per)
                                     : t->pool_stash[i];
@@ -2287,8 +2271,8 @@ int nb_trainer_run(nb_trainer* t, const int32_t* perm_dev, int32_t n_epochs,
 int nb_trainer_run_fleet(nb_trainer* t, const int32_t* const* perm_dev_of,
                          int32_t n_epochs, int32_t* status_host,
                          void* stream) {
-  hipStream_t s = (hipStream_t)stream;
   const long long n = t->ns[0];
+  const EpochSteps es = epoch_steps(n, t->batch);
   TrainArgs a;
   a.nets = t->nets_dev;
   a.X = (const nb_gd*)t->Xs[0]; a.y = (const nb_gd*)t->ys[0];
@@ -2300,89 +2284,12 @@ int nb_trainer_run_fleet(nb_trainer* t, const int32_t* const* perm_dev_of,
   a.sched_jobs = a.sched ? a.sched + 2 * XCD_SLOTS : nullptr;
   a.n = n; a.n_dim = t->n_dim; a.kt1 = t->kt1; a.n_epochs = n_epochs;
   a.max_iter = t->max_iter; a.n_iter_no_change = t->n_iter_no_change;
-  a.batch = (int)((n < t->batch) ? n : t->batch);
+  a.batch = es.batch;
   a.tol = t->tol; a.lr = t->lr; a.b1 = t->b1; a.b2 = t->b2; a.eps = t->eps;
-  const int steps_per_epoch = (int)((n + a.batch - 1) / a.batch);
-  if (!t->two_launch) {
-    FleetData fleet;
-    for (int i = 0; i < MAX_RESIDENT; ++i) {
-      const int k = i < t->E ? i : 0;
-      fleet.d[i].X = (const nb_gd*)t->Xs[k];
-      fleet.d[i].y = (const nb_gd*)t->ys[k];
-      fleet.d[i].perm = (const nb_gi*)perm_dev_of[k];
-      fleet.d[i].n = t->ns[k];
-      fleet.d[i].batch = (int)((t->ns[k] < t->batch) ? t->ns[k] : t->batch);
-    }
-    NB_HIP_CHECK(hipMemsetAsync(t->sync_dev, 0, SYNC_INTS * sizeof(int), s));
-    SyncTable tab;
-    for (int i = 0; i < MAX_RESIDENT; ++i) tab.rec[i] = t->sync_dev;
-    for (int x = 0; x < XCD_COUNT; ++x)
-      for (int w = 0; w < 2; ++w) {
-        const int net = t->xcd_map.net[x][w];
-        if (net < 0) continue;
-        tab.rec[net] = sync_arena()
-            ? g_arena + g_place_of_xcd[x] * ARENA_PLACE_INTS +
-                  (x * 2 + w) * SYNC_WORDS
-            : t->sync_dev + SYNC_WORDS * net;
-        if (tab.rec[net] != t->sync_dev + SYNC_WORDS * net)
-          NB_HIP_CHECK(hipMemsetAsync(tab.rec[net], 0,
-                                      SYNC_WORDS * sizeof(int), s));
-      }
-    // 32 workgroups per XCD: all of them for its network, or 16 for each of
-    // its two
-    const dim3 grid(XCD_COUNT * XCD_SLOTS), blk(256);
-    const int rc = nb_tile_dispatch<NB_MAX_AUG_DT>(t->kt1, [&](auto kt1) {
-      if (t->large)
-        hipLaunchKernelGGL((nb_train_xcd_kernel<kt1(), true>), grid, blk, 0, s,
-                           a, fleet, t->xcd_map, tab, t->sync_dev);
-      else
-        hipLaunchKernelGGL((nb_train_xcd_kernel<kt1(), false>), grid, blk, 0, s,
-                           a, fleet, t->xcd_map, tab, t->sync_dev);
-      return NB_OK;
-    });
-    if (rc != NB_OK) return rc;
-    t->t_adam += (long long)n_epochs * steps_per_epoch;
-    NB_HIP_CHECK(hipGetLastError());
-    if (status_host != nullptr)
-      return nb_trainer_status(t, status_host, stream);
-    return NB_OK;
-  }
-  // two launches per step: one training set, contiguous shuffles
-  for (int i = 1; i < t->E; ++i)
-    if (perm_dev_of[i] != perm_dev_of[0] + (size_t)i * n_epochs * n) {
-      nb_set_error("two-launch training needs the shuffles of all networks "
-                   "in one (E, n_epochs, n) array");
-      return NB_ERR_ARG;
-    }
-  for (int ep = 0; ep < n_epochs; ++ep) {
-    for (int sidx = 0; sidx < steps_per_epoch; ++sidx) {
-      const long long start = (long long)sidx * a.batch;
-      const int nb = (int)((n - start < a.batch) ? (n - start) : a.batch);
-      // (all G_ROWT row tiles: the ones past the end of a short minibatch
-      // clear their delta rows; LARGE: the row tiles of the minibatch)
-      const dim3 gfb(t->large ? (nb + 15) / 16 : G_ROWT, t->E),
-          gg(t->n_jobs, t->E), blk(256);
-      t->t_adam += 1;
-      const int rc = nb_tile_dispatch<NB_MAX_AUG_DT>(t->kt1, [&](auto kt1) {
-        if (t->large)
-          hipLaunchKernelGGL((nb_train_fb_kernel<kt1(), true>), gfb, blk, 0, s,
-                             a, ep, start, nb);
-        else
-          hipLaunchKernelGGL((nb_train_fb_kernel<kt1(), false>), gfb, blk, 0, s,
-                             a, ep, start, nb);
-        return NB_OK;
-      });
-      if (rc != NB_OK) return rc;
-      if (t->large)
-        hipLaunchKernelGGL(nb_train_g_kernel<true>, gg, blk, 0, s, a, nb,
-                           t->t_adam);
-      else
-        hipLaunchKernelGGL(nb_train_g_kernel<false>, gg, blk, 0, s, a, nb,
-                           t->t_adam);
-    }
-    hipLaunchKernelGGL(nb_train_epoch_kernel, dim3(t->E), dim3(64), 0, s, a,
-                       t->t_adam);
-  }
+  const int rc = t->two_launch
+      ? run_two_launch(t, a, perm_dev_of, es.steps, (hipStream_t)stream)
+      : run_resident(t, a, perm_dev_of, es.steps, (hipStream_t)stream);
+  if (rc != NB_OK) return rc;
   NB_HIP_CHECK(hipGetLastError());
   if (status_host != nullptr) return nb_trainer_status(t, status_host, stream);
   return NB_OK;
@@ -2484,7 +2391,7 @@ int nb_dbg_train_times(long long* out) {
 
 int nb_trainer_destroy(nb_trainer* t) {
   if (t == nullptr) return NB_OK;
-  if (t->block_alloc) (void)hipFree(t->block_alloc);
+  if (t->block) (void)hipFree(t->block);
   if (t->big_stash) (void)hipFree(t->big_stash);
   g_xcd_in_use &= ~t->xcd_owned;
   if (t->pin_scal) (void)hipHostFree(t->pin_scal);

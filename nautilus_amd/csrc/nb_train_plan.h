@@ -1,9 +1,10 @@
 // Host arithmetic of the emulator trainer (nb_mlp_train.hip): where a weight
-// lives in the tile-major buffers, and which workgroup updates which weight
-// tile in the gradient phase.  Plain C++17 without HIP, so that
-// tests/train_plan_check.cpp builds it on its own; internal linkage, like the
-// rest of the trainer's one translation unit.  The includer brings the layer
-// shapes (nb_common.h; the test program its own):
+// lives in the tile-major buffers, which workgroup updates which weight tile
+// in the gradient phase, which XCDs a resident trainer owns, how its device
+// memory is laid out and how many steps an epoch has.  Plain C++17 without
+// HIP, so that tests/train_plan_check.cpp builds it on its own; internal
+// linkage, like the rest of the trainer's one translation unit.  The includer
+// brings the layer shapes (nb_common.h; the test program its own):
 #pragma once
 
 #include <algorithm>
@@ -277,6 +278,119 @@ void g_plan(int kt1, int f_lo, int f_sh, std::vector<int>& jobs,
     sched[2 * best.late_slot[j] + 1] = (int)jobs.size() / G_JOB_INTS;
     jobs.insert(jobs.end(), rec, rec + G_JOB_INTS);
   }
+}
+
+// ---- XCD ownership ----------------------------------------------------------
+constexpr int XCD_COUNT = 8;
+constexpr int MAX_RESIDENT = 16;   // networks of one resident launch
+// networks of the XCDs: up to two per XCD (two workgroups per CU), -1 = none
+// (the resident kernel takes it by value)
+struct XcdMap {
+  int n_nets;
+  int net[XCD_COUNT][2];
+};
+
+// A resident network takes one workgroup slot on every CU of an XCD (of two
+// per CU).  Every trainer owns its XCDs exclusively -- two resident kernels
+// that each hold a part of an XCD could wait for each other -- and puts
+// one network on each while they last, two beyond that (16 networks on the
+// 8 XCDs); a trainer that finds too few free XCDs trains with two launches
+// per step instead.  in_use: the XCDs of the live resident trainers;
+// resident_allowed: no switch asks for two launches and workgroups are dealt
+// out over the XCDs as the resident kernel expects.
+// owned: the XCDs of `map`, which the caller adds to in_use.
+struct XcdPlan { bool two_launch; unsigned owned; XcdMap map; };
+XcdPlan plan_xcds(int n_networks, unsigned in_use, bool resident_allowed) {
+  int xs[XCD_COUNT], n_free = 0;                 // the free XCDs, lowest first
+  for (int x = 0; x < XCD_COUNT; ++x)
+    if (!(in_use & (1u << x))) xs[n_free++] = x;
+  XcdPlan p;
+  p.two_launch = n_networks > MAX_RESIDENT || !resident_allowed ||
+                 n_networks > 2 * n_free;
+  p.owned = 0;
+  p.map.n_nets = n_networks;
+  for (int x = 0; x < XCD_COUNT; ++x) p.map.net[x][0] = p.map.net[x][1] = -1;
+  if (p.two_launch) return p;
+  // as many XCDs as there are networks (up to the free ones), the
+  // networks dealt out round-robin
+  const int n_use = std::min(n_networks, n_free);
+  for (int i = 0; i < n_networks; ++i) p.map.net[xs[i % n_use]][i / n_use] = i;
+  for (int j = 0; j < n_use; ++j) p.owned |= 1u << xs[j];
+  return p;
+}
+
+// ---- layout of the device memory --------------------------------------------
+// units of the activations / deltas of the layers 1-4 in the stash (the bias
+// unit included, padded to 16)
+constexpr int LD1 = 112, LD2 = 64, LD3 = 32, LD4 = 16;
+constexpr int SMALL_BATCH = 200;    // largest batch of the compile-time layout
+static_assert(SMALL_BATCH <= MAXB, "the stash in the pool holds MAXB rows");
+// doubles of a stash of `rows` rows (a multiple of 16), `ld0` input units:
+// A0 A1 A2 A3 D1 D2 D3 D4  (constexpr: host and device)
+constexpr long long stash_doubles(long long rows, int ld0) {
+  return rows * (ld0 + 2 * (LD1 + LD2 + LD3) + LD4);
+}
+
+// ONE allocation for everything the kernels touch -- [barrier counters, 12
+// KB][network records, 1 KB][job lists, 1 + 2 KB][weights, moments, stash, loss
+// curve and scalars of every network] -- so that the small arrays lie the
+// same way relative to each other and to the pool in every process (as
+// separate allocations they landed wherever the allocator had a slot, and
+// the step time followed).  (The includer checks its counters and network
+// records against OFF_NETS and OFF_JOBS.)
+constexpr size_t OFF_NETS = 12288, OFF_JOBS = 13312, OFF_SCHED = 14336,
+                 OFF_POOL = 32768;
+// bytes for the job list without a schedule / for [schedule][its job records]
+constexpr size_t JOBS_SLOT = OFF_SCHED - OFF_JOBS,
+                 SCHED_SLOT = OFF_POOL - OFF_SCHED;
+static_assert(OFF_NETS < OFF_JOBS && OFF_JOBS < OFF_SCHED &&
+              OFF_SCHED < OFF_POOL, "trainer block layout");
+
+// a network's part of the pool: the offsets of its buffers, as they lie, and
+// its size, in doubles (n_w: doubles of the weight tiles)
+struct PoolLayout { long long W, M, V, WT, stash, curve, scal, per_net; };
+PoolLayout pool_layout(int kt1, long long n_w, int max_iter) {
+  PoolLayout p;
+  p.W = 0; p.M = n_w; p.V = 2 * n_w; p.WT = 3 * n_w;
+  p.stash = p.WT + (long long)net_layer(4, 1, kt1).wt_off;
+  p.curve = p.stash + stash_doubles(MAXB, 16 * kt1);
+  p.scal = p.curve + ((max_iter + 1) & ~1LL);         // 16-byte alignment
+  // (32 scalars; a multiple of 4 KB: no line of one network's record next to
+  // another's)
+  p.per_net = (p.scal + 32 + 511) / 512 * 512;
+  return p;
+}
+
+// bytes of the block (whole 2 MB fragments: the mapping of a block that ends
+// inside one was seen to cost up to a microsecond per step)
+size_t block_bytes(long long per_net, int n_networks) {
+  const size_t frag = 2u << 20;
+  return (OFF_POOL + (size_t)per_net * n_networks * sizeof(double) + frag - 1) /
+         frag * frag;
+}
+
+// The stash follows the largest minibatch any network sees (batch clipped to
+// its rows, as scikit-learn does): up to SMALL_BATCH rows the stash in the
+// pool (G_ROWT row tiles), beyond it one laid out for the batch, with the
+// loss partials of its row tiles behind it.
+struct StashChoice { bool large; int rowt; };
+StashChoice stash_choice(const std::vector<long long>& rows, int batch) {
+  long long eff = 0;
+  for (long long n : rows) eff = std::max(eff, std::min(n, (long long)batch));
+  const bool large = eff > SMALL_BATCH;
+  return {large, large ? (int)((eff + 15) / 16) : G_ROWT};
+}
+// doubles of one network in a large stash of `rowt` row tiles
+long long large_per_net(int rowt, int kt1) {
+  return (stash_doubles(16LL * rowt, 16 * kt1) + rowt + 511) / 512 * 512;
+}
+
+// ---- steps ------------------------------------------------------------------
+// the minibatch of a network of n rows and its Adam steps per epoch
+struct EpochSteps { int batch, steps; };
+EpochSteps epoch_steps(long long n, int batch) {
+  const int b = (int)std::min(n, (long long)batch);
+  return {b, (int)((n + b - 1) / b)};
 }
 
 }  // namespace

@@ -172,10 +172,9 @@ class Trainer:
             perms_dev = torch.from_numpy(flat).cuda()
             offs = np.concatenate([[0], np.cumsum(
                 [p.size for p in perms])[:-1]])
-            ptrs = (C.c_void_p * self.e)(*[
-                perms_dev.data_ptr() + 4 * int(o) for o in offs])
             _lib.check(self._lib.nb_trainer_run_fleet(
-                self._h, ptrs, n_epochs, status if sync else None, stream))
+                self._h, self._perm_pointers(perms_dev, offs), n_epochs,
+                status if sync else None, stream))
         else:
             perms_dev = torch.from_numpy(
                 np.ascontiguousarray(perms, dtype=np.int32)).cuda()
@@ -185,15 +184,18 @@ class Trainer:
         self._perms = getattr(self, '_perms', [])[-1:] + [perms_dev]
         return np.array(status[:]) if sync else None
 
+    def _perm_pointers(self, perms_dev, offsets):
+        """per network: where its orders start in the int32 tensor"""
+        return (C.c_void_p * self.e)(*[
+            perms_dev.data_ptr() + 4 * int(o) for o in offsets])
+
     def run_async(self, perms_dev, offsets, n_epochs):
         """Enqueue ``n_epochs`` epochs whose orders sit in the int32 cuda
         tensor ``perms_dev`` (network i from element offsets[i]); returns the
         ticket for ``wait`` (``nb_trainer_run_async``)."""
-        ptrs = (C.c_void_p * self.e)(*[
-            perms_dev.data_ptr() + 4 * int(o) for o in offsets])
         ticket = C.c_int64()
         _lib.check(self._lib.nb_trainer_run_async(
-            self._h, ptrs, n_epochs,
+            self._h, self._perm_pointers(perms_dev, offsets), n_epochs,
             C.c_void_p(torch.cuda.current_stream().cuda_stream),
             C.byref(ticket)))
         return ticket.value

@@ -1,7 +1,9 @@
 """The host arithmetic of the emulator trainer (nautilus_amd/csrc/
 nb_train_plan.h, the very header nb_mlp_train.hip includes), built for the
 host by tests/train_plan_check.cpp: which workgroup updates which weight tile
-in the gradient phase, and where a weight lives in the tile-major buffers.
+in the gradient phase, where a weight lives in the tile-major buffers, which
+XCDs a resident trainer owns, the layout of its device memory and the steps
+of an epoch.
 
 ``g_job`` of the trainer has a body for five block shapes and runs a record
 of any other shape as 1 x 1, leaving tiles without their Adam step: the
@@ -21,9 +23,6 @@ GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'train_plan.json')
 H = (100, 50, 20, 1)                     # outputs of the four layers
 HT = (7, 4, 2, 1)                        # ... in 16-wide tiles
 SHAPES = {(1, 1), (2, 1), (1, 2), (3, 1), (2, 2)}    # (nk, nh) g_job runs
-XCD_SLOTS, G_ROWT = 32, 13
-# the slots nb_trainer_create_fleet checks the lists against (bytes)
-JOBS_SLOT, SCHED_SLOT = 14336 - 13312, 32768 - 14336
 
 
 def layer_tiles(kt1):
@@ -42,6 +41,14 @@ def exe(tmp_path_factory):
          '-I', os.path.join(ROOT, 'nautilus_amd', 'csrc'),
          os.path.join(ROOT, 'tests', 'train_plan_check.cpp'), '-o', path])
     return path
+
+
+@pytest.fixture(scope='module')
+def consts(exe):
+    """the header's constants by name: XCD_SLOTS, G_ROWT, the bytes of the
+    slots nb_trainer_create_fleet checks the job lists against, ..."""
+    out = subprocess.check_output([exe, 'consts'], text=True)
+    return {name: int(v) for name, v in (l.split() for l in out.splitlines())}
 
 
 @pytest.fixture(scope='module')
@@ -101,26 +108,27 @@ def check_jobs(jobs, kt1):
 
 
 @pytest.mark.parametrize('kt1', range(1, 10))
-def test_every_tile_has_one_job_of_a_shape_g_job_runs(planned, kt1):
+def test_every_tile_has_one_job_of_a_shape_g_job_runs(planned, consts, kt1):
     rounds = records(planned['rounds'][str(kt1)])
     check_jobs(rounds, kt1)
     assert len(rounds) <= 32                 # two rounds of 16 workgroups
-    assert 4 * 5 * len(rounds) <= JOBS_SLOT
+    assert 4 * 5 * len(rounds) <= consts['JOBS_SLOT']
     check_jobs(chosen(planned, kt1)[0], kt1)
 
 
 @pytest.mark.parametrize('kt1', range(1, 10))
-def test_schedule(planned, kt1):
+def test_schedule(planned, consts, kt1):
     jobs, sched = chosen(planned, kt1)
-    assert len(sched) == 2 * XCD_SLOTS
+    assert len(sched) == 2 * consts['XCD_SLOTS']
     early, late = sched[0::2], sched[1::2]
     assert sorted(j for j in early + late if j >= 0) == list(range(len(jobs)))
-    assert all(j == -1 for j in early[:G_ROWT])   # these run FB meanwhile
+    # these run FB meanwhile
+    assert all(j == -1 for j in early[:consts['G_ROWT']])
     assert all(jobs[j][0] in (1, 2, 3) for j in early if j >= 0)
     assert all(jobs[j][0] == 0 for j in late if j >= 0)
     assert all(j >= -1 for j in sched)
     # [schedule][its job records] in one slot
-    assert 4 * (len(sched) + 5 * len(jobs)) <= SCHED_SLOT
+    assert 4 * (len(sched) + 5 * len(jobs)) <= consts['SCHED_SLOT']
 
 
 def test_job_counts(planned):
@@ -191,3 +199,125 @@ def test_pack_network(exe, tmp_path, n_dim, kt1):
     # every weight and bias at its place, 0.0 everywhere else
     assert np.array_equal(w, want)
     assert np.array_equal(wt, want_t)
+
+
+# ---- XCD ownership (plan_xcds) ----------------------------------------------
+@pytest.fixture(scope='module')
+def xcd_plans(exe):
+    """(n, mask, allowed) -> (two_launch, owned, net[XCD][place])"""
+    out = np.array(subprocess.check_output([exe, 'xcds'], text=True).split(),
+                   dtype=np.int64).reshape(-1, 5 + 16)
+    return {(int(r[0]), int(r[1]), bool(r[2])):
+            (bool(r[3]), int(r[4]), r[5:].reshape(8, 2).tolist())
+            for r in out}
+
+
+def test_xcd_ownership_rule(xcd_plans, consts):
+    """every network count up to one past the resident limit, every set of
+    XCDs in use, resident form allowed or not"""
+    n_xcd, limit = consts['XCD_COUNT'], consts['MAX_RESIDENT']
+    assert (n_xcd, limit) == (8, 16)
+    assert sorted(xcd_plans) == [(n, m, a) for n in range(1, limit + 2)
+                                 for m in range(1 << n_xcd)
+                                 for a in (False, True)]
+    for (n, mask, allowed), (two, owned, net) in xcd_plans.items():
+        case = (n, mask, allowed)
+        free = [x for x in range(n_xcd) if not mask >> x & 1]
+        assert two == (n > limit or not allowed or n > 2 * len(free)), case
+        places = [v for pair in net for v in pair if v >= 0]
+        if two:
+            assert places == [] and owned == 0, case
+            continue
+        assert sorted(places) == list(range(n)), case   # one place each
+        used = [x for x in range(n_xcd) if net[x][0] >= 0 or net[x][1] >= 0]
+        assert owned & mask == 0, case
+        assert owned == sum(1 << x for x in used), case
+        assert all(net[x][0] >= 0 for x in used), case  # place 0 first
+        assert used == free[:len(used)], case           # the lowest free ones
+        assert len(used) == min(n, len(free)), case
+        for i in range(n):
+            assert net[used[i % len(used)]][i // len(used)] == i, case
+
+
+def test_xcd_ownership_cases(xcd_plans):
+    none = [-1, -1]
+    two, owned, net = xcd_plans[4, 0x00, True]
+    assert (two, owned) == (False, 0x0f)
+    assert net == [[0, -1], [1, -1], [2, -1], [3, -1]] + 4 * [none]
+    two, owned, net = xcd_plans[16, 0x00, True]
+    assert (two, owned) == (False, 0xff)
+    assert net == [[x, 8 + x] for x in range(8)]
+    two, owned, net = xcd_plans[9, 0x00, True]
+    assert (two, owned) == (False, 0xff)
+    assert net == [[0, 8]] + [[x, -1] for x in range(1, 8)]
+    two, owned, net = xcd_plans[5, 0x0f, True]
+    assert (two, owned) == (False, 0xf0)
+    assert net == 4 * [none] + [[0, 4], [1, -1], [2, -1], [3, -1]]
+    for mask in (0x0f, 0xf0, 0x55, 0xc3):             # four XCDs free
+        assert xcd_plans[9, mask, True] == (True, 0, 8 * [none])
+        assert not xcd_plans[8, mask, True][0]
+    assert xcd_plans[17, 0x00, True] == (True, 0, 8 * [none])
+    assert xcd_plans[1, 0xff, True] == (True, 0, 8 * [none])
+    assert xcd_plans[4, 0x00, False] == (True, 0, 8 * [none])
+
+
+# ---- layout of the block (pool_layout, block_bytes) --------------------------
+def test_pool_layout(exe, consts):
+    """W, M, V, WT, stash, loss curve and the 32 scalars of a network lie in
+    that order without overlap inside per_net doubles, and the block holds
+    the pools of all networks behind the small arrays"""
+    out = np.array(subprocess.check_output([exe, 'layout'], text=True).split(),
+                   dtype=np.int64).reshape(-1, 12)
+    assert [(int(r[0]), int(r[1])) for r in out] == \
+        [(kt1, m) for kt1 in range(1, 10) for m in (1, 2, 9999, 10000)]
+    # units of a stash row: the input block, activations and deltas of the
+    # layers 1-3 with their bias unit, the output delta, each padded to 16
+    pad16 = lambda u: (u + 15) // 16 * 16
+    upper = 2 * sum(pad16(h + 1) for h in H[:3]) + pad16(H[3])
+    for kt1, max_iter, w, m, v, wt, stash, curve, scal, per_net, b1, b16 in \
+            out.tolist():
+        tiles = layer_tiles(kt1)
+        n_w = 256 * sum(k * h for k, h in tiles)
+        sizes = [n_w, n_w, n_w, 256 * sum(k * h for k, h in tiles[1:]),
+                 16 * consts['G_ROWT'] * (16 * kt1 + upper), max_iter, 32]
+        at = [w, m, v, wt, stash, curve, scal]
+        assert at[0] == 0
+        for i in range(7):
+            end = at[i + 1] if i < 6 else per_net
+            assert at[i] + sizes[i] <= end, (kt1, max_iter, i)
+        assert per_net % 512 == 0
+        assert per_net - (scal + 32) < 512            # no more than rounding
+        assert curve % 2 == 0 and scal % 2 == 0       # 16-byte boundaries
+        for n_networks, bytes_ in ((1, b1), (16, b16)):
+            need = consts['OFF_POOL'] + 8 * n_networks * per_net
+            assert bytes_ % (2 << 20) == 0
+            assert need <= bytes_ < need + (2 << 20)
+
+
+# ---- large stash (stash_choice, large_per_net) -------------------------------
+@pytest.mark.parametrize('rows, batch, large, rowt', [
+    ((1000,), 200, False, 13), ((1000,), 201, True, 13),
+    ((1000,), 209, True, 14), ((1000,), 512, True, 32),
+    ((300,), 4096, True, 19), ((50, 5000), 1000, True, 63),
+    ((150,), 4096, False, 13)])
+def test_stash_choice(exe, consts, rows, batch, large, rowt):
+    assert consts['G_ROWT'] == 13 and consts['SMALL_BATCH'] == 200
+    for kt1 in (1, 4, 9):
+        got = subprocess.check_output(
+            [exe, 'stash', str(kt1), str(batch)] + [str(n) for n in rows],
+            text=True).split()
+        assert (bool(int(got[0])), int(got[1])) == (large, rowt)
+        # the stash of rowt row tiles and the loss partial of each
+        per_net = int(got[2])
+        stash = 16 * rowt * (16 * kt1 + 2 * (112 + 64 + 32) + 16)
+        assert per_net % 512 == 0
+        assert 0 <= per_net - (stash + rowt) < 512
+
+
+@pytest.mark.parametrize('rows, batch, want', [
+    (1000, 512, (512, 2)), (150, 200, (150, 1)), (1000, 200, (200, 5)),
+    (1001, 200, (200, 6)), (1, 200, (1, 1)), (4096, 4096, (4096, 1))])
+def test_epoch_steps(exe, rows, batch, want):
+    got = subprocess.check_output([exe, 'steps', str(rows), str(batch)],
+                                  text=True).split()
+    assert tuple(int(v) for v in got) == want

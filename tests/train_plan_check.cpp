@@ -11,6 +11,21 @@
 //     weight_value(l, k, h), and writes dir/w.bin (pack_network's w), dir/wt.bin
 //     (its transposed tiles) and dir/back.bin (unpack_network of w: coefs and
 //     intercepts of layer 1, of layer 2, ...) as raw doubles
+//   train_plan_check consts
+//     "NAME value" for the constants the tests would otherwise retype
+//   train_plan_check xcds
+//     for n = 1 .. MAX_RESIDENT + 1 networks, every mask of XCDs in use and
+//     resident_allowed = 0, 1: "n mask allowed two_launch owned" and the
+//     network (-1 = none) of place 0, place 1 of XCD 0, of XCD 1, ...
+//   train_plan_check layout
+//     for kt1 = 1 .. 9 and max_iter = 1, 2, 9999, 10000: "kt1 max_iter", the
+//     double offsets W M V WT stash curve scal of pool_layout, per_net, and
+//     the bytes of the block of 1 and of 16 networks
+//   train_plan_check stash kt1 batch rows...
+//     "large rowt per_net": stash_choice of networks with these rows, and
+//     the doubles of one network in a large stash of rowt row tiles
+//   train_plan_check steps rows batch
+//     "batch steps_per_epoch" of epoch_steps
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -96,13 +111,71 @@ int pack(int n_dim, const std::string& dir) {
   return 0;
 }
 
+int consts() {
+  printf("JOBS_SLOT %zu\nSCHED_SLOT %zu\nOFF_POOL %zu\n", JOBS_SLOT, SCHED_SLOT,
+         OFF_POOL);
+  printf("XCD_SLOTS %d\nG_ROWT %d\nXCD_COUNT %d\nMAX_RESIDENT %d\n", XCD_SLOTS,
+         G_ROWT, XCD_COUNT, MAX_RESIDENT);
+  printf("SMALL_BATCH %d\n", SMALL_BATCH);
+  return 0;
+}
+
+int xcds() {
+  for (int n = 1; n <= MAX_RESIDENT + 1; ++n)
+    for (unsigned mask = 0; mask < (1u << XCD_COUNT); ++mask)
+      for (int allowed = 0; allowed < 2; ++allowed) {
+        const XcdPlan p = plan_xcds(n, mask, allowed != 0);
+        printf("%d %u %d %d %u", n, mask, allowed, (int)p.two_launch, p.owned);
+        if (p.map.n_nets != n) return 1;
+        for (int x = 0; x < XCD_COUNT; ++x)
+          printf(" %d %d", p.map.net[x][0], p.map.net[x][1]);
+        printf("\n");
+      }
+  return 0;
+}
+
+int layout() {
+  const int max_iters[4] = {1, 2, 9999, 10000};
+  for (int kt1 = 1; kt1 <= 9; ++kt1)
+    for (int max_iter : max_iters) {
+      const PoolLayout p =
+          pool_layout(kt1, (long long)net_layer(4, 1, kt1).off, max_iter);
+      printf("%d %d %lld %lld %lld %lld %lld %lld %lld %lld %zu %zu\n", kt1,
+             max_iter, p.W, p.M, p.V, p.WT, p.stash, p.curve, p.scal,
+             p.per_net, block_bytes(p.per_net, 1), block_bytes(p.per_net, 16));
+    }
+  return 0;
+}
+
+int stash(int argc, char** argv) {
+  std::vector<long long> rows;
+  for (int i = 4; i < argc; ++i) rows.push_back(atoll(argv[i]));
+  const StashChoice c = stash_choice(rows, atoi(argv[3]));
+  printf("%d %d %lld\n", (int)c.large, c.rowt,
+         large_per_net(c.rowt, atoi(argv[2])));
+  return 0;
+}
+
+int steps(long long rows, int batch) {
+  const EpochSteps e = epoch_steps(rows, batch);
+  printf("%d %d\n", e.batch, e.steps);
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc >= 2 && strcmp(argv[1], "plan") == 0) return plan(argc, argv);
   if (argc == 4 && strcmp(argv[1], "pack") == 0)
     return pack(atoi(argv[2]), argv[3]);
-  fprintf(stderr, "usage: %s plan [late_only shape]... | pack n_dim dir\n",
-          argv[0]);
+  if (argc == 2 && strcmp(argv[1], "consts") == 0) return consts();
+  if (argc == 2 && strcmp(argv[1], "xcds") == 0) return xcds();
+  if (argc == 2 && strcmp(argv[1], "layout") == 0) return layout();
+  if (argc >= 5 && strcmp(argv[1], "stash") == 0) return stash(argc, argv);
+  if (argc == 4 && strcmp(argv[1], "steps") == 0)
+    return steps(atoll(argv[2]), atoi(argv[3]));
+  fprintf(stderr, "usage: %s plan [late_only shape]... | pack n_dim dir | "
+          "consts | xcds | layout | stash kt1 batch rows... | steps rows "
+          "batch\n", argv[0]);
   return 2;
 }
